@@ -10,8 +10,12 @@ synthetic input already resident in HBM.  Prints ONE JSON line on rank 0.
 
 Headline ``value``: the train step at the REFERENCE's precision (fp32
 arithmetic throughout, air/vae.py:5-48, air/air_model.py:533-588), per-GPU
-batch 8192 (the batch configs[1] is quoted on).  Extra keys on the same line
-(rank 0, N = 1 only): ``configs_1_bf16`` (configs[1] itself: bf16 VAE, fp32
+batch 8192 (the batch configs[1] is quoted on).  A plain run sets up, warms
+up, times ``--steps`` steps and prints the headline line (``ms_per_step``: the
+milliseconds one timed step took).  ``--dump-outputs DIR`` also writes what
+the last timed step computed as ``DIR/<name>.npy`` (dump_outputs).
+``--full`` adds every other measurement: ``roofline`` and the extra keys on
+the same line (rank 0, N = 1 only): ``configs_1_bf16`` (configs[1] itself: bf16 VAE, fp32
 elsewhere), ``config_1_batch64_fp32`` (the reference's own batch of 64),
 ``fp32_step_roofline`` (the same step at reference precision against the fp32
 MFMA roof), ``fused_step_roofline`` / ``fused_step_roofline_c64`` (the north-star fused
@@ -242,11 +246,12 @@ def make_asr_model(precision, dev, scope, canvas=50, world=1, rank=0, cfg=None):
 
 
 def timed_train(precision, B, steps, warmup, dev, world=1, rank=0, events=False, scope="bench",
-                model=None, canvas=50, data=None, graph=False):
+                model=None, canvas=50, data=None, graph=False, dump=None):
     """Time `steps` train steps of batch B per rank (after `warmup`); returns
     (seconds, model).  Barrier + synchronize on both sides; the caller takes
     the max over ranks.  data: synthetic() keywords (counts, side).  graph:
-    the captured train step (AIRModel.train_step_graphed; one device)."""
+    the captured train step (AIRModel.train_step_graphed; one device).  dump:
+    directory for the last timed step's outputs (dump_outputs)."""
     if model is None:
         model = make_model(precision, dev, world, rank, scope, canvas=canvas)
     if world > 1:
@@ -270,6 +275,8 @@ def timed_train(precision, B, steps, warmup, dev, world=1, rank=0, events=False,
         dist.barrier()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if dump:
+        dump_outputs(model, dump)
     if events:
         # the roofline's per-launch HIP events over `steps` more steps of the
         # same model and batch (an event pair around each tagged launch costs
@@ -443,6 +450,40 @@ def fp32_step_roofline(batch: int, launches: int, dev):
     return out
 
 
+# --dump-outputs: elements kept of one array (fp32: 16 MiB for the flat
+# parameter / gradient buffers, 4 MiB for a per-image record; 60 MiB in all)
+DUMP_MAX_FLAT = 1 << 22
+DUMP_MAX_RECORD = 1 << 20
+
+
+def dump_outputs(model, out_dir):
+    """What the last timed train step handed its caller, as float32
+    ``out_dir/<name>.npy``: the batch means ``step()`` returns (loss, accuracy,
+    mse), the per-image results, the loop's per-step records, the gradient the
+    step applied and the parameters after it.  Model, canvases and device noise
+    are seeded, so the same arguments give the same step.  An array above its
+    element limit is cut to a fixed seeded sample of its elements (sorted
+    indices, the same for every run of the same shape)."""
+    os.makedirs(out_dir, exist_ok=True)
+    ws = model._ws
+    arrays = {"means": (ws.means, DUMP_MAX_RECORD),
+              "per_image_loss": (model.per_image_loss, DUMP_MAX_RECORD),
+              "reconstruction_loss": (model.reconstruction_loss, DUMP_MAX_RECORD),
+              "rec_num_digits": (model.rec_num_digits, DUMP_MAX_RECORD),
+              "z_pres_probs": (model.z_pres_probs, DUMP_MAX_RECORD),
+              "rec_scales": (model.rec_scales, DUMP_MAX_RECORD),
+              "rec_shifts": (model.rec_shifts, DUMP_MAX_RECORD),
+              "rec_latents": (model.rec_latents, DUMP_MAX_RECORD),
+              "grads": (model.params.grad, DUMP_MAX_FLAT),
+              "params": (model.params.flat, DUMP_MAX_FLAT)}
+    for name, (t, limit) in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > limit:
+            idx = np.sort(np.random.default_rng(20240).choice(a.size, limit, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -451,9 +492,16 @@ def parse():
     ap.add_argument("--batch", type=int, default=8192, help="per-GPU batch (configs[1])")
     ap.add_argument("--precision", default="fp32", choices=["bf16", "fp32"],
                     help="headline precision (fp32 = the reference's arithmetic)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the per-kernel roofline "
+                         "of the timed step, the extra configurations (--extras), the fused-step "
+                         "rooflines and the CPU baseline (--cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--extras", type=int, default=1,
-                    help="N = 1: also time configs[1] (bf16), batch 64, the fused-step rooflines")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+                    help="with --full, N = 1: also time configs[1] (bf16), batch 64, the "
+                         "fused-step rooflines")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="with --full: the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--roofline-batch", type=int, default=65536,
                     help="batch of the stand-alone fused-step roofline runs (0: skip)")
@@ -574,17 +622,20 @@ def main():
 
     B, T = args.batch, 3
     asr = args.workload == "asr_bbox"
+    dump = args.dump_outputs if rank == 0 else None
     if asr:
         T = 6
         el, model = timed_train(args.precision, B, args.steps, args.warmup, dev, world, rank,
-                                events=True, data=ASR_BBOX_DATA,
+                                events=args.full, data=ASR_BBOX_DATA, dump=dump,
                                 model=make_asr_model(args.precision, dev, "bench_asrbb", world=world,
                                                      rank=rank, cfg=ASR_BBOX))
     else:
         el, model = timed_train(args.precision, B, args.steps, args.warmup, dev, world, rank,
-                                events=True)
-    roof = roofline(model.kernel_events, B, args.precision)
-    model.kernel_events = None
+                                events=args.full, dump=dump)
+    roof = None
+    if args.full:
+        roof = roofline(model.kernel_events, B, args.precision)
+        model.kernel_events = None
     if world > 1:
         t = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -619,9 +670,10 @@ def main():
                        "max_steps": T, "data_dependent_steps_would_be": executed,
                        "parallelism": f"dp{world}", "loss_last": loss,
                        "collective_backend": {"nccl": "rccl"}.get(backend, backend)},
-            "roofline": roof,
         }
-        if world == 1 and args.extras and not asr:
+        if args.full:
+            out["roofline"] = roof
+        if args.full and world == 1 and args.extras and not asr:
             if args.precision != "bf16":
                 el2, m2 = timed_train("bf16", B, 10, 3, dev, scope="bench_bf16", events=True)
                 out["configs_1_bf16"] = {
@@ -702,7 +754,7 @@ def main():
                     args.roofline_batch, args.roofline_launches, dev, save=False)
                 out["fp32_step_roofline"] = fp32_step_roofline(args.roofline_batch,
                                                                args.roofline_launches, dev)
-        if args.cpu_baseline and world == 1 and not asr:
+        if args.full and args.cpu_baseline and world == 1 and not asr:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -1,6 +1,6 @@
 #!/bin/bash
-# Round profile (ROUND=r06 names the output directory and the evidence files): rocprofv3 --kernel-trace --stats of the default bench
-# command, then per workload (scripts/prof_one.py) a kernel trace and separate
+# Round profile (ROUND=r06 names the output directory and the evidence files): rocprofv3 --kernel-trace --stats of the full bench
+# command (bench.py --full), then per workload (scripts/prof_one.py) a kernel trace and separate
 # FETCH_SIZE / WRITE_SIZE passes, each under its own time limit; stops at the
 # first failure.  scripts/pmc_tables.py turns the passes into tables and the
 # bench's pmc_summary.json entries.
@@ -11,7 +11,7 @@ R=${ROUND:-r06}
 O=gpurun_out/${R}prof
 rm -rf $O; mkdir -p $O
 if [ "${SKIP_BENCH_TRACE:-0}" != 1 ]; then
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -o run -- python3 bench.py > $O/bench.log 2>&1 || { echo "bench trace failed"; tail -5 $O/bench.log; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -o run -- python3 bench.py --full > $O/bench.log 2>&1 || { echo "bench trace failed"; tail -5 $O/bench.log; exit 1; }
 echo "bench trace ok"
 fi
 for W in "fused_bf16 65536 50" "fused_bf16 65536 64" "step_fp32 8192" "step_bf16 8192"; do

@@ -6,7 +6,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-CMD="python3 bench.py --steps 5 --warmup 2 --cpu-baseline 0 --roofline-launches 5"
+CMD="python3 bench.py --full --steps 5 --warmup 2 --cpu-baseline 0 --roofline-launches 5"
 rm -rf gpurun_out/prof gpurun_out/pmc_fetch gpurun_out/pmc_write
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run -- $CMD > gpurun_out/prof.log 2>&1 || { echo "trace failed"; exit 1; }
 echo "trace ok"
