@@ -28,10 +28,11 @@ import torch
 
 from . import _lib
 from . import ops
-from .ops import EPI_RELU, EPI_SIGMOID_NOISE, EPI_SOFTPLUS, EPI_SOFTPLUS_BWD, EPI_STORE, gemm
+from .ops import EPI_RELU, gemm
 from .graph import GraphCapture
 from .params import ParamStore, param_specs
 from .results import Results
+from .vae import GlimpseVAE
 from .wgrads import WeightGradients
 
 _ops = ops._ops  # torch.ops.mog_air (csrc/torch_ops.cpp)
@@ -176,10 +177,6 @@ class _Workspace:
         HS = m.scale_hidden_units
         e = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
         self.dcanvas = e(B, C2)
-        self.dr = e(B, W2)
-        self.dz = e(B, Z)
-        self.tmp_a2 = e(B, R2)
-        self.dg = e(B, W2)
         if self.bf16:
             eb = lambda *s: torch.empty(s, device=dev, dtype=torch.bfloat16)  # noqa: E731
             Zp = (Z + 7) // 8 * 8
@@ -192,9 +189,9 @@ class _Workspace:
             self.dd2, self.dd1 = e(T, B, G2), e(T, B, G1)
             self.dmu, self.dlv = e(T, B, Z), e(T, B, Z)
             self.da2, self.da1 = e(T, B, R2), e(T, B, R1)
-        self.dth_f, self.dth_b, self.dot = e(B, 6), e(B, 6), e(B)
+        self.dth_f = e(B, 6)  # (AIR-ASR: one step's STN read backward)
         # all loop steps at once (AIR: only the LSTM chain is sequential)
-        self.dr_all, self.dg_all = e(T, B, W2), e(T, B, W2)
+        self.dg_all = e(T, B, W2)
         self.dz_all, self.tmp_a2_all = e(T, B, Z), e(T, B, R2)
         self.dth_f_all, self.dth_b_all, self.dot_all = e(T, B, 6), e(T, B, 6), e(T, B)
         self.dout = e(5, T, B, 2)
@@ -210,7 +207,7 @@ class _Workspace:
         self._bwd = True
 
 
-class AIRModel(WeightGradients, GraphCapture, Results):
+class AIRModel(GlimpseVAE, WeightGradients, GraphCapture, Results):
     """See module docstring.  Extra keyword-only arguments (not in the
     reference): ``device``, ``seed`` (weight init), ``noise_seed`` (device
     Philox noise), ``grad_world`` (data-parallel world size folded into the
@@ -403,8 +400,6 @@ class AIRModel(WeightGradients, GraphCapture, Results):
 
     _HEADS = ("scale/mean", "scale/log_variance", "shift/mean", "shift/log_variance",
               "z_pres/log_odds")
-    _VAE = ("recognition_1", "recognition_2", "rec_mean", "rec_log_variance", "generative_1",
-            "generative_2", "gen_mean")
 
     def _fill_noise(self, ws: _Workspace, noise: Optional[Dict[str, torch.Tensor]]):
         ws.eps_x_offset = None  # injected noise: every consumer reads the buffers
@@ -545,10 +540,8 @@ class AIRModel(WeightGradients, GraphCapture, Results):
                     self._step_fused(X, ws, t, float(lik_std), save=need_grad)
                 continue
             # STN read -> glimpse VAE (air_model.py:523-550, vae.py:5-48)
-            if self.precision == "bf16":
-                self._vae_forward_bf16(X, ws, t, float(lik_std))
-            else:
-                self._vae_forward_fp32(X, ws, t, float(lik_std))
+            self._vae_encoder(X, ws, t, t + 1, ws.runloss)
+            self._vae_decoder(ws, float(lik_std), t, t + 1)
             # STN write + masked canvas accumulation (air_model.py:580-588, 665-675)
             ops.stn_forward(ws.r[t], ws.th_b[t], (C, C), out=ws.canvas, z=ws.zval[t],
                             mask=ws.zmask[t], accumulate=True)
@@ -600,158 +593,6 @@ class AIRModel(WeightGradients, GraphCapture, Results):
         straddle two steps (B % 64)."""
         return self.batch_vae and B % 64 == 0
 
-    FUSED_F32_MIN_ROWS = 8192
-
-    def _vae_forward_all(self, X, ws, lik_std, t0=0, t1=None, save=True):
-        """The glimpse VAE (STN read -> VAE -> STN write into the canvas
-        parts) of loop steps [t0, t1) as one set of launches over their rows.
-        save=False: no backward follows (the fused kernel skips the saved
-        activations)."""
-        B, C, W = ws.B, self.canvas_size, self.windows_size
-        t1 = self.max_steps if t1 is None else t1
-        T, TB = t1 - t0, (t1 - t0) * B
-        W2, R1, R2, Z, G1, G2 = self._vae_dims()
-        r_ = lambda a: a[t0:t1]  # noqa: E731
-        if self.fused_step:
-            self._pack_bf16()
-            if self.windows_size != 28 or (R1, R2, Z, G1, G2) != (512, 256, 50, 256, 512):
-                raise ValueError("the fused step kernel is compiled for the reference VAE shape")
-            wt = [self._wf[n] for n in self._VAE]
-            gen = getattr(ws, "eps_x_offset", None) is not None
-            off = ws.eps_x_offset + t0 * B * (W2 // 4) if gen else 0
-            bias = [self._P("vae/" + n + "/biases") for n in self._VAE]
-            # forward only (no backward follows): the backward's saved
-            # activations are not written (vae_step.hip moves its own bytes)
-            sv = r_ if save else (lambda a: None)  # noqa: E731
-            with self._timed("stn_vae_step_all"):
-                self._stn_vae_step_bf16(TB, C, X, r_, sv, gen, off, wt, bias, lik_std, ws, B)
-            return
-        # the fused fp32 kernel runs one 32-row tile per workgroup with a long
-        # serial chain per tile (~200 us): below one tile per CU (T*B < 8192
-        # rows, e.g. the reference's batch of 64) the unfused launches, which
-        # spread every layer over the chip, finish first -- same bits either way
-        if self.precision == "fp32" and self.fused_f32 and TB >= self.FUSED_F32_MIN_ROWS:
-            self._pack_f32()
-            gen = getattr(ws, "eps_x_offset", None) is not None
-            off = ws.eps_x_offset + t0 * B * (W2 // 4) if gen else 0
-            bias = [self._P("vae/" + n + "/biases") for n in self._VAE]
-            # (the pre-activations are not stored: None in their slots)
-            saved = [r_(getattr(ws, n)) if save and n is not None else None
-                     for n in ("g", None, "a1", None, "a2", "mu", "lv", None, "d1", None, "d2")]
-            with self._timed("stn_vae_step_f32_all"):
-                _ops.stn_vae_step_f32_(TB, C, X, r_(ws.th_f), r_(ws.th_b), r_(ws.zmask),
-                                       r_(ws.zval), r_(ws.eps_z), r_(ws.eps_x),
-                                       ops._i64(self.noise_seed), ops._i64(off), gen, self._wf32,
-                                       bias, lik_std, float(self.vae_prior_mean),
-                                       float(self.vae_prior_variance), self.vae_prior_log_variance,
-                                       r_(ws.cparts), r_(ws.prows), None, r_(ws.vkl), saved,
-                                       r_(ws.z), r_(ws.r), B)
-            return
-        v = lambda a: a[t0:t1].reshape(TB, -1)  # noqa: E731
-        vb = {n: self._P("vae/" + n + "/biases") for n in self._VAE}
-        if self.precision == "bf16":
-            from .ops import BF_SIGMOID_NOISE, BF_SOFTPLUS, BF_STORE, gemm_bf16
-            Zp = self._pad8(Z)
-            self._pack_bf16()
-            wt = self._wt
-            # every step's glimpse read of the shared input canvas in one launch
-            ops.stn_forward(X, v(ws.th_f), (W, W), out=v(ws.gb), n=TB)
-            gemm_bf16([v(ws.gb)], [wt["recognition_1"]], [v(ws.a1b)], TB, R1, W2, W2, W2, R1,
-                      epi=BF_SOFTPLUS, bias=[vb["recognition_1"]])
-            gemm_bf16([v(ws.a1b)], [wt["recognition_2"]], [v(ws.a2b)], TB, R2, R1, R1, R1, R2,
-                      epi=BF_SOFTPLUS, bias=[vb["recognition_2"]])
-            gemm_bf16([v(ws.a2b), v(ws.a2b)], [wt["rec_mean"], wt["rec_log_variance"]],
-                      [v(ws.mu), v(ws.lv)], TB, Z, R2, R2, R2, Z, epi=BF_STORE,
-                      bias=[vb["rec_mean"], vb["rec_log_variance"]])
-            self._vae_sample_fwd_all(ws, v(ws.zb), Zp, t0, t1)
-            gemm_bf16([v(ws.zb)], [wt["generative_1"]], [v(ws.d1b)], TB, G1, Zp, Zp, Zp, G1,
-                      epi=BF_SOFTPLUS, bias=[vb["generative_1"]])
-            gemm_bf16([v(ws.d1b)], [wt["generative_2"]], [v(ws.d2b)], TB, G2, G1, G1, G1, G2,
-                      epi=BF_SOFTPLUS, bias=[vb["generative_2"]])
-            gemm_bf16([v(ws.d2b)], [wt["gen_mean"]], [v(ws.r)], TB, W2, G2, G2, G2, W2,
-                      epi=BF_SIGMOID_NOISE, bias=[vb["gen_mean"]], aux=[v(ws.eps_x)], ldaux=W2,
-                      aux_scale=lik_std)
-        else:
-            vw = {n: self._P("vae/" + n + "/weights") for n in self._VAE}
-            ops.stn_forward(X, v(ws.th_f), (W, W), out=v(ws.g), n=TB)
-            gemm([v(ws.g)], [vw["recognition_1"]], [v(ws.a1)], TB, R1, W2, W2, R1, R1,
-                 epi=EPI_SOFTPLUS, bias=[vb["recognition_1"]])
-            gemm([v(ws.a1)], [vw["recognition_2"]], [v(ws.a2)], TB, R2, R1, R1, R2, R2,
-                 epi=EPI_SOFTPLUS, bias=[vb["recognition_2"]])
-            if self._latent_nt(TB):
-                # a small batch: the latent layers as NT products of W^T copies
-                # (N = Z / K = Z miss the LDS-DMA alignment, and their row-major
-                # form ran on 64 x 64 tiles, a few workgroups); the same
-                # k-ordered chains, so the same bits
-                wt = self._vae_wT()
-                gemm([v(ws.a2), v(ws.a2)], [wt[0], wt[1]], [v(ws.mu), v(ws.lv)], TB, Z, R2, R2,
-                     R2, Z, transB=True, bias=[vb["rec_mean"], vb["rec_log_variance"]])
-                self._vae_sample_fwd_all(ws, None, 0, t0, t1)
-                gemm([v(ws.z)], [wt[2]], [v(ws.d1)], TB, G1, Z, Z, Z, G1, transB=True,
-                     epi=EPI_SOFTPLUS, bias=[vb["generative_1"]])
-            else:
-                gemm([v(ws.a2), v(ws.a2)], [vw["rec_mean"], vw["rec_log_variance"]],
-                     [v(ws.mu), v(ws.lv)], TB, Z, R2, R2, Z, Z,
-                     bias=[vb["rec_mean"], vb["rec_log_variance"]])
-                self._vae_sample_fwd_all(ws, None, 0, t0, t1)
-                gemm([v(ws.z)], [vw["generative_1"]], [v(ws.d1)], TB, G1, Z, Z, G1, G1,
-                     epi=EPI_SOFTPLUS, bias=[vb["generative_1"]])
-            gemm([v(ws.d1)], [vw["generative_2"]], [v(ws.d2)], TB, G2, G1, G1, G2, G2,
-                 epi=EPI_SOFTPLUS, bias=[vb["generative_2"]])
-            if ws.eps_x_offset is not None:
-                # eps_x of steps t0.. in the epilogue: [T, B, W2] fill order
-                ops.gemm_sigmoid_philox(v(ws.d2), vw["gen_mean"], v(ws.r), vb["gen_mean"], TB, W2,
-                                        G2, G2, W2, W2, lik_std, self.noise_seed,
-                                        ws.eps_x_offset + t0 * B * W2 // 4)
-            else:
-                gemm([v(ws.d2)], [vw["gen_mean"]], [v(ws.r)], TB, W2, G2, G2, W2, W2,
-                     epi=EPI_SIGMOID_NOISE, bias=[vb["gen_mean"]],
-                     aux=[v(ws.eps_x)], ldaux=W2, aux_scale=lik_std)
-        # STN write of every step into its canvas part (air_model.py:580-588);
-        # the loss kernel adds the parts in step order (:665-675)
-        _ops.stn_write_parts_(v(ws.r), TB, W, W, r_(ws.th_b), C, C, r_(ws.zval), r_(ws.zmask),
-                              r_(ws.cparts), r_(ws.prows))
-
-    def _vae_wT(self):
-        """W^T of rec_mean, rec_log_variance [Z][R2] and generative_1 [G1][Z],
-        transposed in one launch when the parameters changed (a captured step
-        records the launch: GraphCapture._capture resets the version)."""
-        W2, R1, R2, Z, G1, G2 = self._vae_dims()
-        buf = self.__dict__.get("_vae_wT_buf")
-        if buf is None:
-            buf = self.__dict__["_vae_wT_buf"] = [
-                torch.empty((Z, R2), device=self.device), torch.empty((Z, R2), device=self.device),
-                torch.empty((G1, Z), device=self.device)]
-        if getattr(self, "_vae_wT_version", None) != self.params.version:
-            _ops.transpose32_batch_(buf, [self._P("vae/" + n + "/weights") for n in
-                                          ("rec_mean", "rec_log_variance", "generative_1")])
-            self._vae_wT_version = self.params.version
-        return buf
-
-    def _latent_nt(self, rows):
-        """The latent layers as NT products of W^T copies (_vae_wT) below
-        SIDE_MIN_BATCH rows: their N or K = Z misses the LDS-DMA alignment."""
-        return self.vae_latent_dimensions % 4 != 0 and rows < self.SIDE_MIN_BATCH
-
-    def _stn_vae_step_bf16(self, TB, C, X, r_, sv, gen, off, wt, bias, lik_std, ws, B):
-        """The bf16 fused step over the TB rows of loop steps r_ (x row = row % B)."""
-        _ops.stn_vae_step_(TB, C, X, r_(ws.th_f), r_(ws.th_b), r_(ws.zmask), r_(ws.zval),
-                           r_(ws.eps_z), r_(ws.eps_x), ops._i64(self.noise_seed), ops._i64(off),
-                           gen, wt, bias, lik_std, float(self.vae_prior_mean),
-                           float(self.vae_prior_variance), self.vae_prior_log_variance,
-                           r_(ws.cparts), r_(ws.prows), None, r_(ws.vkl), sv(ws.gb), sv(ws.a1b),
-                           sv(ws.a2b), sv(ws.mu), sv(ws.lv), r_(ws.z), sv(ws.zb), sv(ws.d1b),
-                           sv(ws.d2b), r_(ws.r), B)
-
-    def _vae_sample_fwd_all(self, ws, zb, ldzb, t0=0, t1=None):
-        t1 = self.max_steps if t1 is None else t1
-        TB = ws.B * (t1 - t0)
-        r_ = lambda a: a[t0:t1]  # noqa: E731
-        _ops.vae_sample_forward_(TB, self.vae_latent_dimensions, float(self.vae_prior_mean),
-                                 float(self.vae_prior_variance), self.vae_prior_log_variance,
-                                 r_(ws.mu), r_(ws.lv), r_(ws.eps_z), r_(ws.z), zb, ldzb,
-                                 r_(ws.zmask), None, r_(ws.vkl))
-
     def _forward_loss(self, X, targets, ws, need_grad, outputs=True):
         """reconstruction loss (air_model.py:866-900) + batch means.  With
         outputs=False (train steps) the clipped reconstruction and, in the
@@ -786,21 +627,21 @@ class AIRModel(WeightGradients, GraphCapture, Results):
         """Every loop step's glimpse-path backward (STN write, VAE, STN read,
         heads) depends only on that step's records and dL/dcanvas, so it runs
         once over all T*B rows; only the LSTM chain is sequential."""
-        B, T, H = ws.B, self.max_steps, self.rnn_units
-        C, W, C2 = self.canvas_size, self.windows_size, self.C2
-        HS = self.scale_hidden_units
-        TB = T * B
         st = self.params
         # the gradient buffer and the LSTM chain's dG sum, zeroed in one launch
         # (the fp32 x3p x-rows gradient reads every step's dG instead of the
         # sum: mog_split3_sum_bf16)
-        if self._x3p_xgrad(B):
+        if self._x3p_xgrad(ws.B):
             _ops.fill32_batch_([st.grad], [0])
         else:
             _ops.fill32_batch_([st.grad, ws.dGsum], [0, 0])
-        # small batch, one GPU: the fp32-chain weight gradients are collected
-        # and run as one grouped launch at the end (_wgrad_group_end)
-        self._wgroup = (self._wgroup_obj if (self.WGRAD_GROUP and B < self.SIDE_MIN_BATCH
+        self._backward_body_grouped(X, ws)
+
+    def _backward_body_grouped(self, X, ws) -> None:
+        """_backward_body; small batch, one GPU: the fp32-chain weight
+        gradients it meets are collected (_dw) and run as one grouped launch
+        at the end."""
+        self._wgroup = (self._wgroup_obj if (self.WGRAD_GROUP and ws.B < self.SIDE_MIN_BATCH
                                              and self.grad_reducer is None) else None)
         wg = self._wgroup
         if wg is not None:
@@ -830,12 +671,23 @@ class AIRModel(WeightGradients, GraphCapture, Results):
             g = self.__dict__["_wgroup_obj_"] = ops.WgradGroup()
         return g
 
+    def _stn_write_backward_all(self, ws) -> None:
+        """Every loop step's STN write backward in one launch over T*B rows
+        against the shared canvas gradient (it reads only the forward's
+        records); the glimpse cotangent leaves through the VAE's output
+        sigmoid straight from the kernel (dm fp32 / dmb bf16: bit-identical
+        to dU followed by mog_sigmoid_backward)."""
+        TB, C = self.max_steps * ws.B, self.canvas_size
+        dm = ws.dmb if self.precision == "bf16" else ws.dm
+        ops.stn_backward(ws.r.view(TB, -1), ws.th_b, (C, C), ws.dcanvas, gscale=ws.zc,
+                         dtheta=ws.dth_b_all, dot=ws.dot_all, want_dot=True, n=TB,
+                         dm=dm.view(TB, -1))
+
     def _backward_body(self, X: torch.Tensor, ws: _Workspace) -> None:
         B, T, H = ws.B, self.max_steps, self.rnn_units
-        C, W, C2 = self.canvas_size, self.windows_size, self.C2
+        W, C2 = self.windows_size, self.C2
         HS = self.scale_hidden_units
         TB = T * B
-        st = self.params
         K = self._P("rnn/basic_lstm_cell/kernel")
         bK = self._P("rnn/basic_lstm_cell/bias")
         Wh = K[C2:]
@@ -846,19 +698,9 @@ class AIRModel(WeightGradients, GraphCapture, Results):
         temperature = self.hyper("z_pres_temperature")
         # STN write backward of all steps against the shared canvas gradient
         with self._timed("stn_write_bwd", self._stn_bwd_work(TB, write=True)):
-            if self.precision == "bf16":
-                # dr leaves through the output sigmoid as bf16 straight from the kernel
-                ops.stn_backward(ws.r.view(TB, -1), ws.th_b, (C, C), ws.dcanvas, gscale=ws.zc,
-                                 dtheta=ws.dth_b_all, dot=ws.dot_all, want_dot=True, n=TB,
-                                 dm_bf16=ws.dmb.view(TB, -1))
-            else:  # fp32 dm through the output sigmoid, likewise
-                ops.stn_backward(ws.r.view(TB, -1), ws.th_b, (C, C), ws.dcanvas, gscale=ws.zc,
-                                 dtheta=ws.dth_b_all, dot=ws.dot_all, want_dot=True, n=TB,
-                                 dm=ws.dm.view(TB, -1))
-        if self.precision == "bf16":
-            self._vae_backward_bf16_all(ws, gscale)
-        else:
-            self._vae_backward_fp32_all(ws, gscale)
+            self._stn_write_backward_all(ws)
+        self._vae_decoder_backward(ws, 0, T)
+        self._vae_encoder_backward(ws, 0, T, gscale)
         # The VAE weight gradients need only the activations and the VAE input
         # gradients, final here: they run on a second stream (MFMA-bound
         # split-K GEMMs) under the latency-bound STN read backward and the
@@ -966,7 +808,7 @@ class AIRModel(WeightGradients, GraphCapture, Results):
             torch.cuda.current_stream().wait_stream(self._side_stream())
             torch.cuda.current_stream().wait_stream(self._stream3())
 
-    # single GPU: heads' weight gradients on the side stream (see _backward)
+    # single GPU: heads' weight gradients on the side stream (see _backward_body)
     HEADS_WGRAD_SIDE = True
     # ... and the LSTM kernel's recurrent-rows gradient beside the x-rows one
     REC_WGRAD_SIDE = True
@@ -979,31 +821,6 @@ class AIRModel(WeightGradients, GraphCapture, Results):
     # eager 0.90 -> 1.00 ms, captured 0.60 -> 0.65 ms with them)
     SIDE_MIN_BATCH = 1024
 
-    # fp32 configuration: the VAE input gradients dX = dY W^T of the 256- to
-    # 784-wide layers on the bf16 matrix cores with exact three-piece splits
-    # (gemm_x3.hip NT form: dY split in the kernel, W split once per optimizer
-    # step) -- the chain is on the step's critical path; fp32-level accuracy
-    # like the weight gradients.  False: the fp32 MFMA GEMMs.
-    VAE_DX_X3 = True
-    _X3_DX = ("gen_mean", "generative_2", "recognition_2", "recognition_1")
-
-    def _w3(self):
-        """The three bf16 pieces of the VAE weights the x3 input gradients read
-        (W [in][out] -> [3][in][out]), refreshed when the parameters change."""
-        if getattr(self, "_w3_version", None) != self.params.version:
-            if getattr(self, "_w3_buf", None) is None:
-                self._w3_buf = {}
-                for n in self._X3_DX:
-                    I, O = self._P("vae/" + n + "/weights").shape
-                    self._w3_buf[n] = torch.empty((3, I, O), device=self.device,
-                                                  dtype=torch.bfloat16)
-            for n in self._X3_DX:
-                w = self._P("vae/" + n + "/weights")
-                I, O = w.shape
-                ops.split3_bf16(w, self._w3_buf[n], I, O, O, O, I * O)
-            self._w3_version = self.params.version
-        return self._w3_buf
-
     def _stn_bwd_work(self, rows, write):
         """Algorithmic HBM bytes of one STN backward launch over `rows` image-
         steps: write -- r and dm (C2... of the glimpse), the
@@ -1015,312 +832,6 @@ class AIRModel(WeightGradients, GraphCapture, Results):
             dm = 2 if self.precision == "bf16" else 4
             return ("hbm", rows * (W2 * 4 + W2 * dm + C2 * 4 / T + 52), None)
         return ("hbm", rows * (C2 * 4 / T + W2 * 4 + 48), None)
-
-    def _dx(self, dY, name, out, M, N, K, aux=None):
-        """out[M,N] = dY W^T (W = vae/name/weights [N][K]) [* sigmoid(aux)]."""
-        if self.VAE_DX_X3 and K % 8 == 0 and N % 4 == 0 and M >= self.X3_DX_MIN_ROWS:
-            w3 = self._w3()[name]
-            # six bf16 MFMA products per fp32 product (gemm_x3.hip)
-            with self._timed("vae_dgrad_x3", ("mfma", 2.0 * M * N * K, "fp32", "x3")):
-                ops.gemm_x3_nt(dY, w3, N * K, out, M, N, K, K, K, N, aux=aux,
-                               ldaux=N if aux is not None else 0)
-            return
-        with self._timed("vae_dgrad_f32", ("mfma", 2.0 * M * N * K, "fp32")):
-            gemm([dY], [self._P("vae/" + name + "/weights")], [out], M, N, K, K, K, N, transB=True,
-                 epi=EPI_SOFTPLUS_BWD if aux is not None else EPI_STORE,
-                 aux=[aux] if aux is not None else None, ldaux=N if aux is not None else 0)
-
-    def _vae_backward_fp32_all(self, ws, gscale):
-        TB = ws.B * self.max_steps
-        W2, R1, R2, Z, G1, G2 = self._vae_dims()
-        vw = {n: self._P("vae/" + n + "/weights") for n in self._VAE}
-        # dm = SigmoidGrad(r, dr) was written by the STN write backward
-        # (aux = the softplus outputs: epi 4 / NT epi 1 take sigmoid(x) as
-        # 1 - exp(-softplus(x)))
-        self._dx(ws.dm, "gen_mean", ws.dd2, TB, G2, W2, aux=ws.d2)
-        self._dx(ws.dd2, "generative_2", ws.dd1, TB, G1, G2, aux=ws.d1)
-        gemm([ws.dd1], [vw["generative_1"]], [ws.dz_all], TB, Z, G1, G1, G1, Z, transB=True)
-        _ops.vae_sample_backward_(TB, Z, float(self.vae_prior_mean),
-                                  float(self.vae_prior_variance), float(gscale), ws.mu, ws.lv,
-                                  ws.eps_z, ws.dz_all, ws.zmask, ws.dmu, ws.dlv, None, None, 0)
-        gemm([ws.dmu], [vw["rec_mean"]], [ws.tmp_a2_all], TB, R2, Z, Z, Z, R2, transB=True)
-        gemm([ws.dlv], [vw["rec_log_variance"]], [ws.da2], TB, R2, Z, Z, Z, R2,
-             transB=True, epi=EPI_SOFTPLUS_BWD, Cin=[ws.tmp_a2_all], aux=[ws.a2], ldaux=R2)
-        self._dx(ws.da2, "recognition_2", ws.da1, TB, R1, R2, aux=ws.a1)
-        self._dx(ws.da1, "recognition_1", ws.dg_all, TB, W2, R1)
-
-    def _vae_backward_bf16_all(self, ws, gscale):
-        from .ops import BF_SOFTPLUS_BWD, BF_STORE, gemm_bf16
-        TB = ws.B * self.max_steps
-        W2, R1, R2, Z, G1, G2 = self._vae_dims()
-        Zp = self._pad8(Z)
-        wn = self._wn
-        # dmb = bf16(SigmoidGrad(r, dr)) was written by the STN write backward
-        gemm_bf16([ws.dmb], [wn["gen_mean"]], [ws.dd2b], TB, G2, W2, W2, W2, G2,
-                  epi=BF_SOFTPLUS_BWD, aux=[ws.d2b], ldaux=G2)
-        gemm_bf16([ws.dd2b], [wn["generative_2"]], [ws.dd1b], TB, G1, G2, G2, G2, G1,
-                  epi=BF_SOFTPLUS_BWD, aux=[ws.d1b], ldaux=G1)
-        gemm_bf16([ws.dd1b], [wn["generative_1"]], [ws.dz_all], TB, Z, G1, G1, G1, Z,
-                  epi=BF_STORE)
-        _ops.vae_sample_backward_(TB, Z, float(self.vae_prior_mean),
-                                  float(self.vae_prior_variance), float(gscale), ws.mu, ws.lv,
-                                  ws.eps_z, ws.dz_all, ws.zmask, None, None, ws.dmub, ws.dlvb, Zp)
-        gemm_bf16([ws.dmub], [wn["rec_mean"]], [ws.tmp_a2_all], TB, R2, Zp, Zp, Zp, R2,
-                  epi=BF_STORE)
-        gemm_bf16([ws.dlvb], [wn["rec_log_variance"]], [ws.da2b], TB, R2, Zp, Zp, Zp, R2,
-                  epi=BF_SOFTPLUS_BWD, Cin=[ws.tmp_a2_all], aux=[ws.a2b], ldaux=R2)
-        gemm_bf16([ws.da2b], [wn["recognition_2"]], [ws.da1b], TB, R1, R2, R2, R2, R1,
-                  epi=BF_SOFTPLUS_BWD, aux=[ws.a1b], ldaux=R1)
-        gemm_bf16([ws.da1b], [wn["recognition_1"]], [ws.dg_all], TB, W2, R1, R1, R1, W2,
-                  epi=BF_STORE)
-
-    # ------------------------------------------------------ glimpse VAE ----
-    def _vae_dims(self):
-        R1, R2 = self.vae_recognition_units
-        G1, G2 = self.vae_generative_units
-        return self.W2, R1, R2, self.vae_latent_dimensions, G1, G2
-
-    def _vae_forward_fp32(self, X, ws, t, lik_std):
-        self._vae_encoder_fp32(X, ws, t)
-        self._vae_decoder_fp32(ws, lik_std, t, t + 1)
-
-    def _vae_encoder_fp32(self, X, ws, t):
-        """STN read -> recognition layers -> z sample of loop step t."""
-        B, W = ws.B, self.windows_size
-        W2, R1, R2, Z, G1, G2 = self._vae_dims()
-        vw = {n: self._P("vae/" + n + "/weights") for n in self._VAE}
-        vb = {n: self._P("vae/" + n + "/biases") for n in self._VAE}
-        ops.stn_forward(X, ws.th_f[t], (W, W), out=ws.g[t])
-        gemm([ws.g[t]], [vw["recognition_1"]], [ws.a1[t]], B, R1, W2, W2, R1, R1,
-             epi=EPI_SOFTPLUS, bias=[vb["recognition_1"]])
-        gemm([ws.a1[t]], [vw["recognition_2"]], [ws.a2[t]], B, R2, R1, R1, R2, R2,
-             epi=EPI_SOFTPLUS, bias=[vb["recognition_2"]])
-        if self._latent_nt(B):
-            wt = self._vae_wT()
-            gemm([ws.a2[t], ws.a2[t]], wt[:2], [ws.mu[t], ws.lv[t]], B, Z, R2, R2, R2, Z,
-                 transB=True, bias=[vb["rec_mean"], vb["rec_log_variance"]])
-        else:
-            gemm([ws.a2[t], ws.a2[t]], [vw["rec_mean"], vw["rec_log_variance"]],
-                 [ws.mu[t], ws.lv[t]], B, Z, R2, R2, Z, Z,
-                 bias=[vb["rec_mean"], vb["rec_log_variance"]])
-        self._vae_sample_fwd(ws, t, None, 0)
-
-    def _vae_decoder_fp32(self, ws, lik_std, t0, t1):
-        """Generative layers of loop steps [t0, t1) over their rows at once
-        (rows are independent: the same chains as step by step)."""
-        W2, R1, R2, Z, G1, G2 = self._vae_dims()
-        n = (t1 - t0) * ws.B
-        v = lambda a: a[t0:t1].reshape(n, -1)  # noqa: E731
-        vw = {k: self._P("vae/" + k + "/weights") for k in self._VAE[4:]}
-        vb = {k: self._P("vae/" + k + "/biases") for k in self._VAE[4:]}
-        if self._latent_nt(n):
-            gemm([v(ws.z)], [self._vae_wT()[2]], [v(ws.d1)], n, G1, Z, Z, Z, G1, transB=True,
-                 epi=EPI_SOFTPLUS, bias=[vb["generative_1"]])
-        else:
-            gemm([v(ws.z)], [vw["generative_1"]], [v(ws.d1)], n, G1, Z, Z, G1, G1,
-                 epi=EPI_SOFTPLUS, bias=[vb["generative_1"]])
-        gemm([v(ws.d1)], [vw["generative_2"]], [v(ws.d2)], n, G2, G1, G1, G2, G2,
-             epi=EPI_SOFTPLUS, bias=[vb["generative_2"]])
-        gemm([v(ws.d2)], [vw["gen_mean"]], [v(ws.r)], n, W2, G2, G2, W2, W2,
-             epi=EPI_SIGMOID_NOISE, bias=[vb["gen_mean"]],
-             aux=[v(ws.eps_x)], ldaux=W2, aux_scale=lik_std)
-
-    def _vae_sample_fwd(self, ws, t, zb, ldzb):
-        _ops.vae_sample_forward_(ws.B, self.vae_latent_dimensions, float(self.vae_prior_mean),
-                                 float(self.vae_prior_variance), self.vae_prior_log_variance,
-                                 ws.mu[t], ws.lv[t], ws.eps_z[t], ws.z[t], zb, ldzb,
-                                 ws.zmask[t], ws.runloss, ws.vkl[t])
-
-    def _dz_hook(self, ws, t, dz):
-        """Extra gradient reaching the latent z of step t (in dz) before the
-        sample backward (none in AIR; the ASR model adds the next step's
-        LSTM-input gradient here)."""
-
-    def _vae_decoder_backward_all(self, ws):
-        """The decoder half of every loop step's VAE backward over all T*B
-        rows (dm -> dd2 -> dd1 -> dz_all; dm already through the output
-        sigmoid), for a loop that needs only the encoder half per step: the
-        AIR-ASR reversed loop, whose dz_t takes the next step's carry (the
-        same chains as the per-step launches, so the same values)."""
-        T, B = self.max_steps, ws.B
-        TB = T * B
-        W2, R1, R2, Z, G1, G2 = self._vae_dims()
-        if getattr(ws, "dz_all", None) is None:
-            ws.dz_all = torch.empty((T, B, Z), device=self.device)
-        v = lambda x: x.view(TB, -1)  # noqa: E731
-        if self.precision == "bf16":
-            from .ops import BF_SOFTPLUS_BWD, BF_STORE, gemm_bf16
-            wn = self._wn
-            gemm_bf16([v(ws.dmb)], [wn["gen_mean"]], [v(ws.dd2b)], TB, G2, W2, W2, W2, G2,
-                      epi=BF_SOFTPLUS_BWD, aux=[v(ws.d2b)], ldaux=G2)
-            gemm_bf16([v(ws.dd2b)], [wn["generative_2"]], [v(ws.dd1b)], TB, G1, G2, G2, G2, G1,
-                      epi=BF_SOFTPLUS_BWD, aux=[v(ws.d1b)], ldaux=G1)
-            gemm_bf16([v(ws.dd1b)], [wn["generative_1"]], [v(ws.dz_all)], TB, Z, G1, G1, G1, Z,
-                      epi=BF_STORE)
-        else:
-            self._dx(v(ws.dm), "gen_mean", v(ws.dd2), TB, G2, W2, aux=v(ws.d2))
-            self._dx(v(ws.dd2), "generative_2", v(ws.dd1), TB, G1, G2, aux=v(ws.d1))
-            gemm([v(ws.dd1)], [self._P("vae/generative_1/weights")], [v(ws.dz_all)], TB, Z, G1, G1,
-                 G1, Z, transB=True)
-        ws.dec_ready = True
-
-    def _vae_backward_fp32(self, ws, t, gscale):
-        B = ws.B
-        W2, R1, R2, Z, G1, G2 = self._vae_dims()
-        vw = {n: self._P("vae/" + n + "/weights") for n in self._VAE}
-        if getattr(ws, "dec_ready", False):  # (the decoder half ran over T*B rows)
-            dz = ws.dz_all[t]
-        else:
-            dz = ws.dz
-            if not getattr(ws, "dm_ready", False):
-                _ops.sigmoid_backward_(ws.r[t], ws.dr, ws.dm[t], B * W2)
-            self._dx(ws.dm[t], "gen_mean", ws.dd2[t], B, G2, W2, aux=ws.d2[t])
-            self._dx(ws.dd2[t], "generative_2", ws.dd1[t], B, G1, G2, aux=ws.d1[t])
-            gemm([ws.dd1[t]], [vw["generative_1"]], [dz], B, Z, G1, G1, G1, Z, transB=True)
-        self._dz_hook(ws, t, dz)
-        _ops.vae_sample_backward_(B, Z, float(self.vae_prior_mean),
-                                  float(self.vae_prior_variance), float(gscale), ws.mu[t],
-                                  ws.lv[t], ws.eps_z[t], dz, ws.zmask[t], ws.dmu[t], ws.dlv[t],
-                                  None, None, 0)
-        gemm([ws.dmu[t]], [vw["rec_mean"]], [ws.tmp_a2], B, R2, Z, Z, Z, R2, transB=True)
-        gemm([ws.dlv[t]], [vw["rec_log_variance"]], [ws.da2[t]], B, R2, Z, Z, Z, R2,
-             transB=True, epi=EPI_SOFTPLUS_BWD, Cin=[ws.tmp_a2], aux=[ws.a2[t]], ldaux=R2)
-        self._dx(ws.da2[t], "recognition_2", ws.da1[t], B, R1, R2, aux=ws.a1[t])
-        self._dx(ws.da1[t], "recognition_1", ws.dg, B, W2, R1)
-
-    # bf16 configuration: VAE GEMM operands bf16 (fp32 accumulate), activations
-    # stored bf16 (post-activation only: softplus' = 1 - exp(-softplus)), the
-    # LSTM / heads / STN / canvas / losses stay fp32 (SURVEY.md §8 D.5).
-    @staticmethod
-    def _pad8(n):
-        return (n + 7) // 8 * 8
-
-    def _pack_bf16(self):
-        """Refresh the bf16 weight packs after a parameter update (one batched
-        launch): wn[name] = W [in][out8] (dX B operand) and either
-        wf[name] = W^T in MFMA B-fragment order (fused step kernel) or
-        wt[name] = W^T [out][in8] (unfused forward GEMMs)."""
-        if getattr(self, "_pack_version", None) == self.params.version:
-            return
-        if not hasattr(self, "_pack_args"):
-            bf = dict(device=self.device, dtype=torch.bfloat16)
-            self._wt, self._wn, self._wf = {}, {}, {}
-            srcs, dsts, dims = [], [], []
-            for n in self._VAE:
-                w = self._P("vae/" + n + "/weights")
-                I, O = w.shape
-                wn = self._wn[n] = torch.zeros((I, self._pad8(O)), **bf)
-                if self.fused_step:
-                    Np, Kp = (O + 15) // 16 * 16, (I + 31) // 32 * 32
-                    wf = self._wf[n] = torch.zeros((Np, Kp), **bf)
-                    fwd, fdims = wf, [I, O, O, Np, Kp, Kp, 2]
-                else:
-                    wt = self._wt[n] = torch.zeros((O, self._pad8(I)), **bf)
-                    fwd, fdims = wt, [I, O, O, O, wt.shape[1], wt.shape[1], 1]
-                srcs += [w, w]
-                dsts += [fwd, wn]
-                dims += fdims + [I, O, O, I, wn.shape[1], wn.shape[1], 0]
-            self._pack_args = (srcs, dsts, dims)
-        _ops.cvt_bf16_batch_(*self._pack_args)
-        self._pack_version = self.params.version
-
-    def _pack_f32(self):
-        """Refresh the fp32 MFMA B-fragment packs of the VAE weights (the fp32
-        fused step's weight operand) after a parameter update: one launch."""
-        if getattr(self, "_pack32_version", None) == self.params.version:
-            return
-        if not hasattr(self, "_pack32_args"):
-            ws_, ks, ns, outs = [], [], [], []
-            for n in self._VAE:
-                w = self._P("vae/" + n + "/weights")
-                K, N = w.shape
-                ws_.append(w)
-                ks.append(int(K))
-                ns.append(int(N))
-                outs.append(torch.empty(((K + 15) // 16) * ((N + 15) // 16) * 256,
-                                        device=self.device))
-            self._wf32 = outs
-            self._pack32_args = (ws_, ks, ns, outs)
-        _ops.pack_frag_f32_(*self._pack32_args)
-        self._pack32_version = self.params.version
-
-    def _vae_forward_bf16(self, X, ws, t, lik_std):
-        from .ops import BF_SIGMOID_NOISE, BF_SOFTPLUS, BF_STORE, gemm_bf16
-        B, W = ws.B, self.windows_size
-        W2, R1, R2, Z, G1, G2 = self._vae_dims()
-        Zp = self._pad8(Z)
-        self._pack_bf16()
-        wt = self._wt
-        vb = {n: self._P("vae/" + n + "/biases") for n in self._VAE}
-        ops.stn_forward(X, ws.th_f[t], (W, W), out=ws.gb[t])
-        gemm_bf16([ws.gb[t]], [wt["recognition_1"]], [ws.a1b[t]], B, R1, W2, W2, W2, R1,
-                  epi=BF_SOFTPLUS, bias=[vb["recognition_1"]])
-        gemm_bf16([ws.a1b[t]], [wt["recognition_2"]], [ws.a2b[t]], B, R2, R1, R1, R1, R2,
-                  epi=BF_SOFTPLUS, bias=[vb["recognition_2"]])
-        gemm_bf16([ws.a2b[t], ws.a2b[t]], [wt["rec_mean"], wt["rec_log_variance"]],
-                  [ws.mu[t], ws.lv[t]], B, Z, R2, R2, R2, Z, epi=BF_STORE,
-                  bias=[vb["rec_mean"], vb["rec_log_variance"]])
-        self._vae_sample_fwd(ws, t, ws.zb[t], Zp)
-        gemm_bf16([ws.zb[t]], [wt["generative_1"]], [ws.d1b[t]], B, G1, Zp, Zp, Zp, G1,
-                  epi=BF_SOFTPLUS, bias=[vb["generative_1"]])
-        gemm_bf16([ws.d1b[t]], [wt["generative_2"]], [ws.d2b[t]], B, G2, G1, G1, G1, G2,
-                  epi=BF_SOFTPLUS, bias=[vb["generative_2"]])
-        gemm_bf16([ws.d2b[t]], [wt["gen_mean"]], [ws.r[t]], B, W2, G2, G2, G2, W2,
-                  epi=BF_SIGMOID_NOISE, bias=[vb["gen_mean"]], aux=[ws.eps_x[t]], ldaux=W2,
-                  aux_scale=lik_std)
-
-    def _step_fused(self, X, ws, t, lik_std, save=True):
-        """STN read + VAE + latent sample/KL + STN write-accumulate in one launch
-        (vae_step.hip; same arithmetic as the unfused bf16 sequence).
-        save=False: forward only, the backward's activations are not written."""
-        W2, R1, R2, Z, G1, G2 = self._vae_dims()
-        self._pack_bf16()
-        if self.windows_size != 28 or (R1, R2, Z, G1, G2) != (512, 256, 50, 256, 512):
-            raise ValueError("the fused step kernel is compiled for the reference VAE shape")
-        wt = [self._wf[n] for n in self._VAE]
-        gen = getattr(ws, "eps_x_offset", None) is not None
-        off = ws.eps_x_offset + t * ws.B * (W2 // 4) if gen else 0
-        bias = [self._P("vae/" + n + "/biases") for n in self._VAE]
-        _ops.stn_vae_step_(ws.B, self.canvas_size, X, ws.th_f[t], ws.th_b[t], ws.zmask[t],
-                           ws.zval[t], ws.eps_z[t], ws.eps_x[t], ops._i64(self.noise_seed),
-                           ops._i64(off), gen, wt, bias, lik_std, float(self.vae_prior_mean),
-                           float(self.vae_prior_variance), self.vae_prior_log_variance,
-                           ws.cparts[t], ws.prows[t], ws.runloss, ws.vkl[t], ws.gb[t],
-                           *(a[t] if save else None for a in (ws.a1b, ws.a2b, ws.mu, ws.lv)),
-                           ws.z[t], ws.zb[t] if save else None, ws.d1b[t] if save else None,
-                           ws.d2b[t] if save else None, ws.r[t])
-
-    def _vae_backward_bf16(self, ws, t, gscale):
-        from .ops import BF_SOFTPLUS_BWD, BF_STORE, gemm_bf16
-        B = ws.B
-        W2, R1, R2, Z, G1, G2 = self._vae_dims()
-        Zp = self._pad8(Z)
-        wn = self._wn
-        if getattr(ws, "dec_ready", False):  # (the decoder half ran over T*B rows)
-            dz = ws.dz_all[t]
-        else:
-            dz = ws.dz
-            if not getattr(ws, "dm_ready", False):
-                _ops.sigmoid_backward_(ws.r[t], ws.dr, ws.dmb[t], B * W2)
-            gemm_bf16([ws.dmb[t]], [wn["gen_mean"]], [ws.dd2b[t]], B, G2, W2, W2, W2, G2,
-                      epi=BF_SOFTPLUS_BWD, aux=[ws.d2b[t]], ldaux=G2)
-            gemm_bf16([ws.dd2b[t]], [wn["generative_2"]], [ws.dd1b[t]], B, G1, G2, G2, G2, G1,
-                      epi=BF_SOFTPLUS_BWD, aux=[ws.d1b[t]], ldaux=G1)
-            gemm_bf16([ws.dd1b[t]], [wn["generative_1"]], [dz], B, Z, G1, G1, G1, Z,
-                      epi=BF_STORE)
-        self._dz_hook(ws, t, dz)
-        _ops.vae_sample_backward_(B, Z, float(self.vae_prior_mean),
-                                  float(self.vae_prior_variance), float(gscale), ws.mu[t],
-                                  ws.lv[t], ws.eps_z[t], dz, ws.zmask[t], None, None,
-                                  ws.dmub[t], ws.dlvb[t], Zp)
-        gemm_bf16([ws.dmub[t]], [wn["rec_mean"]], [ws.tmp_a2], B, R2, Zp, Zp, Zp, R2,
-                  epi=BF_STORE)
-        gemm_bf16([ws.dlvb[t]], [wn["rec_log_variance"]], [ws.da2b[t]], B, R2, Zp, Zp, Zp, R2,
-                  epi=BF_SOFTPLUS_BWD, Cin=[ws.tmp_a2], aux=[ws.a2b[t]], ldaux=R2)
-        gemm_bf16([ws.da2b[t]], [wn["recognition_2"]], [ws.da1b[t]], B, R1, R2, R2, R2, R1,
-                  epi=BF_SOFTPLUS_BWD, aux=[ws.a1b[t]], ldaux=R1)
-        gemm_bf16([ws.da1b[t]], [wn["recognition_1"]], [ws.dg], B, W2, R1, R1, R1, W2,
-                  epi=BF_STORE)
 
     # the side and third streams are created once per process and device and
     # shared by every model (see _shared_streams)

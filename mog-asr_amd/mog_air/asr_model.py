@@ -103,7 +103,7 @@ class _AsrWorkspace(_Workspace):
             return
         super().alloc_backward(m)
         dev, B = m.device, self.B
-        T, H, Z = m.max_steps, m.rnn_units, m.vae_latent_dimensions
+        T, H = m.max_steps, m.rnn_units
         e = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
         self.dreg = e(T, 4, B)
         self.douts = e(T, B, D_N)
@@ -113,7 +113,7 @@ class _AsrWorkspace(_Workspace):
         self.dGg = e(T, B, 4 * H)
         self.dGgsum = e(B, 4 * H)
         self.dU, self.dUg = e(B, LU), e(B, LU)
-        self.dz_carry, self.dss_carry = e(B, Z), e(B, 3)
+        self.dss_carry = e(B, 3)
 
 
 class AIRModel(_AirBase):
@@ -359,6 +359,7 @@ class AIRModel(_AirBase):
         gen_w = [self._N(n + "/kernel") for n in ("gen_shift/dense", "gen_shift/dense_2")]
         gen_b = [self._N(n + "/bias") for n in ("gen_shift/dense", "gen_shift/dense_2")]
         sc_w = [self._N("inf_scale/dense/kernel")[:H], self._N("inf_scale/dense_2/kernel")[:H]]
+        defer = self.precision == "fp32" and self.DEFER_DECODER
         for t in range(T):
             prev = t > 0
             # both cells' input rows in one launch
@@ -405,21 +406,16 @@ class AIRModel(_AirBase):
             if self._f32_parts(B):
                 self._vae_forward_all(X, ws, lik_std, t, t + 1, save=need_grad)
                 continue
-            if self.precision == "bf16":
-                self._vae_forward_bf16(X, ws, t, lik_std)
-            elif self.DEFER_DECODER:
-                # only z feeds the recurrence: the generative half waits
-                self._vae_encoder_fp32(X, ws, t)
-                continue
-            else:
-                self._vae_forward_fp32(X, ws, t, lik_std)
+            self._vae_encoder(X, ws, t, t + 1, ws.runloss)
+            if defer:
+                continue  # only z feeds the recurrence: the generative half waits
+            self._vae_decoder(ws, lik_std, t, t + 1)
             ops.stn_forward(ws.r[t], ws.th_b[t], (C, C), out=ws.canvas, z=ws.zval[t],
                             mask=ws.zmask[t], accumulate=True)
-        if (self.precision == "fp32" and self.DEFER_DECODER and not self.fused_step
-                and not self._f32_parts(B)):
+        if defer and not self._f32_parts(B):
             # the decoder of every step over T*B rows in one set of launches,
             # then the canvas accumulated in step order (the same bits)
-            self._vae_decoder_fp32(ws, lik_std, 0, T)
+            self._vae_decoder(ws, lik_std, 0, T)
             for t in range(T):
                 ops.stn_forward(ws.r[t], ws.th_b[t], (C, C), out=ws.canvas, z=ws.zval[t],
                                 mask=ws.zmask[t], accumulate=True)
@@ -457,36 +453,12 @@ class AIRModel(_AirBase):
         self._outputs_ready = True
 
     # --------------------------------------------------------- backward ---
-    def _dz_hook(self, ws, t, dz):
-        # (with the batched decoder half, asr_unpack_ added the carry already)
-        if t < self.max_steps - 1 and not getattr(ws, "dec_ready", False):
-            _ops.add_(dz, ws.dz_carry, dz, ws.B * self.vae_latent_dimensions)
-
     def _backward(self, X, ws):
-        # small batch, one GPU: the fp32-chain weight gradients as grouped
-        # launches at the end (as AIRModel._backward)
-        self._wgroup = (self._wgroup_obj if (self.WGRAD_GROUP and ws.B < self.SIDE_MIN_BATCH
-                                             and self.grad_reducer is None) else None)
-        wg = self._wgroup
-        if wg is not None:
-            wg.probs = []  # (a fresh collection: nothing left from a failed step)
-        try:
-            self._backward_body(X, ws)
-        except BaseException:
-            if wg is not None:
-                wg.probs = []  # a failed body's partial problems never launch
-            raise
-        finally:
-            self._wgroup = None
-            ws.dm_ready = ws.dec_ready = False
-        if wg is not None and wg.probs:
-            flops = sum(2.0 * p[4] * p[5] * p[6] for p in wg.probs)
-            with self._timed("wgrad_group", ("mfma", flops, "fp32")):
-                wg.launch()
+        self._backward_body_grouped(X, ws)  # (the body zeroes its own accumulators)
 
     def _backward_body(self, X, ws):
         B, T, H, Z = ws.B, self.max_steps, self.rnn_units, self.vae_latent_dimensions
-        C, W, C2 = self.canvas_size, self.windows_size, self.C2
+        W, C2 = self.windows_size, self.C2
         # the gradient buffer and the LSTM chains' accumulators in one launch
         _ops.fill32_batch_([self.params.grad, ws.dh, ws.dhg, ws.dGsum, ws.dGgsum], [0] * 5)
         Ki = self._Kpad("infer_rnn_running/kernel")
@@ -508,22 +480,13 @@ class AIRModel(_AirBase):
         ws.u_wgrads_done = steps_side and self.U_WGRAD_PER_STEP
         # every step's STN write backward in ONE launch over T*B rows, before
         # the loop (it reads only the forward's records and the canvas
-        # gradient, shared by the steps; AIRModel._backward does the same),
-        # the glimpse gradient taken through the output sigmoid (dm, bit-identical
-        # to dU + mog_sigmoid_backward): six launches of B rows -> one
-        TB = T * B
-        if self.precision == "bf16":
-            ops.stn_backward(ws.r.view(TB, -1), ws.th_b, (C, C), ws.dcanvas, gscale=ws.zc,
-                             dtheta=ws.dth_b_all, dot=ws.dot_all, want_dot=True, n=TB,
-                             dm_bf16=ws.dmb.view(TB, -1))
-        else:
-            ops.stn_backward(ws.r.view(TB, -1), ws.th_b, (C, C), ws.dcanvas, gscale=ws.zc,
-                             dtheta=ws.dth_b_all, dot=ws.dot_all, want_dot=True, n=TB,
-                             dm=ws.dm.view(TB, -1))
-        ws.dm_ready = True
+        # gradient, shared by the steps; the AIR model's _backward_body does
+        # the same): six launches of B rows -> one
+        self._stn_write_backward_all(ws)
         # and the decoder half of every step's VAE backward (dz_t before the
-        # loop's carry), likewise over T*B rows
-        self._vae_decoder_backward_all(ws)
+        # loop's carry), likewise over T*B rows; the reversed loop runs only
+        # the encoder half per step
+        self._vae_decoder_backward(ws, 0, T)
         # a small batch's recurrent-input gradient in DH_PARTS K slices
         # (AIRModel.DH_PARTS: the serial K = 4H chain per workgroup cut)
         parts = self.DH_PARTS if (B < self.SIDE_MIN_BATCH and self.DH_PARTS > 1
@@ -532,10 +495,7 @@ class AIRModel(_AirBase):
             ws.dUp = torch.empty((parts,) + tuple(ws.dU.shape), device=self.device)
             ws.dUgp = torch.empty((parts,) + tuple(ws.dUg.shape), device=self.device)
         for t in reversed(range(T)):
-            if self.precision == "bf16":
-                self._vae_backward_bf16(ws, t, gscale)
-            else:
-                self._vae_backward_fp32(ws, t, gscale)
+            self._vae_encoder_backward(ws, t, t + 1, gscale)
             if steps_side:
                 # step t's VAE weight gradients are final: accumulate them on
                 # the side stream under the rest of the loop
@@ -544,7 +504,7 @@ class AIRModel(_AirBase):
                         self._vae_weight_grads_bf16(ws, t)
                     else:
                         self._vae_weight_grads_fp32(ws, t)
-            ops.stn_backward(X, ws.th_f[t], (W, W), ws.dg, want_dU=False, dtheta=ws.dth_f)
+            ops.stn_backward(X, ws.th_f[t], (W, W), ws.dg_all[t], want_dU=False, dtheta=ws.dth_f)
             hid = [ws.hid8[k, t] for k in range(8)]
             dpre = [ws.dpre[k, t] for k in range(8)]
             _ops.asr_step_backward_(B, self.train, fix, float(self.hyper("z_pres_temperature")),
@@ -597,7 +557,6 @@ class AIRModel(_AirBase):
                 # half is there already: no separate add launch)
                 _ops.asr_unpack_(B, Z, H, LU, ws.dU, ws.dUg, ws.dz_all[t - 1], ws.dss_carry,
                                  ws.dh[t - 1], ws.dhg[t - 1], 1)
-        ws.dm_ready = ws.dec_ready = False
         self._weight_grads(X, ws)
         if steps_side:
             torch.cuda.current_stream().wait_stream(side)

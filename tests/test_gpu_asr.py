@@ -171,6 +171,27 @@ def test_asr_gradients_vs_float64_autograd(kw, precision, tol, cos_min, global_t
                       indent=1)
 
 
+def test_asr_decoder_in_loop_matches_deferred_bitwise():
+    """fp32 below FUSED_F32_MIN_ROWS: the generative half of each step's VAE
+    inside the loop (DEFER_DECODER = False: encoder then decoder of
+    [t, t + 1)) against all steps' decoder after the loop over T*B rows --
+    rows are independent, so the same bits."""
+    cfg, P, nz, x, k = _setup(50)
+    noise = {n: torch.as_tensor(v).to(DEV) for n, v in nz.items()}
+    md, ml = _model(cfg, P, "asrdefer1"), _model(cfg, P, "asrdefer0")
+    ml.DEFER_DECODER = False
+    assert md.DEFER_DECODER and not md._f32_parts(cfg.batch)
+    md.infer(x, k, noise=noise)
+    ml.infer(x, k, noise=noise)
+    torch.cuda.synchronize()
+    for n in ("mu", "lv", "z", "d1", "d2", "r"):
+        a, b = getattr(md._ws, n), getattr(ml._ws, n)
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), n
+    # (-0 vs +0 allowed on the canvas, as in test_batched_vae_matches_per_step_bitwise)
+    np.testing.assert_array_equal(md.canvas.cpu().numpy(), ml.canvas.cpu().numpy())
+    assert md.loss == ml.loss
+
+
 def test_asr_train_steps_finite():
     cfg, P, nz, x, k = _setup(40, batch=64, max_steps=6)
     m = _model(cfg, P, "asrtrain", "bf16")
