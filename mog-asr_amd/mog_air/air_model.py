@@ -1,6 +1,8 @@
 """AIRModel — drop-in host object for the reference's AIR baseline model
 (air/air_model.py:13-1146), running the per-object-step loop on MI355X HIP
-kernels (libmog_air.so) with a hand-scheduled forward and backward.
+kernels (libmog_air.so) with a hand-scheduled forward and backward.  The part
+it shares with the AIR-ASR model (constructor, workspace, streams, noise, the
+public API) is ModelBase (model_base.py); this file is the AIR loop.
 
 Reference surface kept (air_model.py:15-51, training_air_original.py:158-209):
 the constructor keyword arguments, variable sharing between a train model and
@@ -21,47 +23,22 @@ No host synchronisation happens inside a train step.
 from __future__ import annotations
 
 import contextlib
-from typing import Dict, Optional
+from typing import Optional
 
 import numpy as np
 import torch
 
-from . import _lib
 from . import ops
+from .model_base import R_NREC, ModelBase, _Workspace, annealed_value  # noqa: F401
 from .ops import EPI_RELU, gemm
-from .graph import GraphCapture
-from .params import ParamStore, param_specs
-from .results import Results
-from .vae import GlimpseVAE
-from .wgrads import WeightGradients
+from .params import param_specs
+from .results import Generation
 
 _ops = ops._ops  # torch.ops.mog_air (csrc/torch_ops.cpp)
 
-# step-record slots (air_cell.hip enum)
+# step-record slots (air_cell.hip enum; R_NREC of them)
 R_SM, R_SLV, R_HM0, R_HM1, R_HLV0, R_HLV1, R_LO, R_S, R_TX, R_TY, R_Y, R_Z = range(12)
-R_ACT_OLD, R_ACT, R_LIVE, R_ZC, R_ZTERM, R_NREC = 12, 13, 14, 15, 16, 17
-
-_SCOPES: Dict[str, ParamStore] = {}
-
-
-def _f32log(v: float) -> float:
-    return float(np.log(np.float32(v), dtype=np.float32))
-
-
-def annealed_value(schedule: dict, global_step: int, eps=1e-9) -> float:
-    """tf.train.exponential_decay (+min/max/log) in fp32 (air_model.py:164-184)."""
-    f = np.float32
-    p = f(global_step) / f(schedule["iters"])
-    if schedule.get("staircase", False):
-        p = np.floor(p)
-    v = f(schedule["init"]) * np.power(f(schedule["factor"]), p, dtype=np.float32)
-    if "min" in schedule:
-        v = np.maximum(v, f(schedule["min"]))
-    if "max" in schedule:
-        v = np.minimum(v, f(schedule["max"]))
-    if schedule.get("log", False):
-        v = np.log(v + f(eps), dtype=np.float32)
-    return float(v)
+R_ACT_OLD, R_ACT, R_LIVE, R_ZC, R_ZTERM = 12, 13, 14, 15, 16
 
 
 def marginal_objective(num_prior, max_steps) -> np.ndarray:
@@ -87,127 +64,7 @@ def marginal_objective(num_prior, max_steps) -> np.ndarray:
     return obj.astype(np.float32)
 
 
-_STREAMS: Dict[torch.device, tuple] = {}
-
-
-def _shared_streams(device):
-    """The side stream and the third stream of AIRModel, created once per
-    process and device.  HIP places a stream on one of its GPU_MAX_HW_QUEUES
-    (4) hardware queues when the stream is created; with a pair created per
-    model, every other model of a process had both on ONE queue, which
-    serialised the third stream behind the side stream (fp32 step 3.09 ->
-    3.43 ms, bf16 2.09 -> 2.29 ms; scripts/gpu_slot_trace.sh: queues 2 / 3 for
-    the first model, 4 / 4 for the second).  The first pair of a process sits
-    on two queues of its own, and every model now uses it."""
-    key = torch.device(device)
-    if key not in _STREAMS:
-        _STREAMS[key] = (torch.cuda.Stream(device=key), torch.cuda.Stream(device=key))
-    return _STREAMS[key]
-
-
-class _Workspace:
-    """All per-batch device buffers of one train step (HBM-resident, reused).
-    Buffers in ZERO_PADDED carry zero pad columns written once at allocation
-    (the bf16 latents' 50 -> 56 columns: the K padding of the GEMMs that read
-    them); every other element is written by the step before it is read."""
-
-    ZERO_PADDED = ("zb", "dmub", "dlvb", "Xb")
-
-    def __init__(self, m: "AIRModel", B: int):
-        dev = m.device
-        T, H, C2, W2, Z = m.max_steps, m.rnn_units, m.C2, m.W2, m.vae_latent_dimensions
-        R1, R2 = m.vae_recognition_units
-        G1, G2 = m.vae_generative_units
-        HS = m.scale_hidden_units
-        e = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
-        self.B = B
-        self.Gx = e(B, 4 * H)
-        self.G = e(T, B, 4 * H)
-        self.c = e(T, B, H)
-        self.h = e(T, B, H)
-        self.hid = e(5, T, B, HS)
-        self.rec = e(T, R_NREC, B)
-        self.th_f = e(T, B, 6)
-        self.th_b = e(T, B, 6)
-        self.scale = e(T, B)
-        self.shift = e(T, B, 2)
-        self.zprob, self.zkl, self.skl, self.shkl = e(T, B), e(T, B), e(T, B), e(T, B)
-        self.zmask, self.zval, self.vkl = e(T, B), e(T, B), e(T, B)
-        self.zc = e(T, B)
-        self.bf16 = m.precision == "bf16"
-        self.mu, self.lv, self.z = e(T, B, Z), e(T, B, Z), e(T, B, Z)
-        self.r = e(T, B, W2)
-        if self.bf16:
-            eb = lambda *s: torch.empty(s, device=dev, dtype=torch.bfloat16)  # noqa: E731
-            Zp = (Z + 7) // 8 * 8
-            self.gb, self.a1b, self.a2b = eb(T, B, W2), eb(T, B, R1), eb(T, B, R2)
-            self.zb = torch.zeros((T, B, Zp), device=dev, dtype=torch.bfloat16)
-            self.d1b, self.d2b = eb(T, B, G1), eb(T, B, G2)
-        else:
-            self.g = e(T, B, W2)
-            # (post-activations only: the softplus backward reads sigmoid(x)
-            # as 1 - exp(-softplus(x)), mog_gemm_f32 epi 4)
-            self.a1, self.a2 = e(T, B, R1), e(T, B, R2)
-            self.d1, self.d2 = e(T, B, G1), e(T, B, G2)
-        self.canvas = e(B, C2)
-        # fused bf16 step: per-step canvas contributions, summed by the loss kernel
-        parts = m._parts_layout(B)
-        self.cparts = e(T, B, C2) if parts else None
-        self.prows = torch.empty((T, B), device=dev, dtype=torch.int32) if parts else None
-        self.stop, self.runloss = e(B), e(B)
-        self.digits = torch.empty(B, device=dev, dtype=torch.int32)
-        self.live = torch.empty(T + 1, device=dev, dtype=torch.int32)
-        self.recon = e(B, C2)
-        self.bce, self.mse, self.loss_b, self.acc_b = e(B), e(B), e(B), e(B)
-        self.means = e(4)
-        # noise
-        self.eps_scale, self.eps_shift = e(T, B), e(T, B, 2)
-        self.eps_z, self.eps_x, self.u = e(T, B, Z), e(T, B, W2), e(T, B)
-        self.eps_x_offset = None  # set when the fused kernel generates eps_x itself
-        self._bwd = False
-        self.materialized = False
-
-    def alloc_backward(self, m: "AIRModel"):
-        if self._bwd:
-            return
-        dev, B = m.device, self.B
-        T, H, C2, W2, Z = m.max_steps, m.rnn_units, m.C2, m.W2, m.vae_latent_dimensions
-        R1, R2 = m.vae_recognition_units
-        G1, G2 = m.vae_generative_units
-        HS = m.scale_hidden_units
-        e = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
-        self.dcanvas = e(B, C2)
-        if self.bf16:
-            eb = lambda *s: torch.empty(s, device=dev, dtype=torch.bfloat16)  # noqa: E731
-            Zp = (Z + 7) // 8 * 8
-            self.dmb, self.dd2b, self.dd1b = eb(T, B, W2), eb(T, B, G2), eb(T, B, G1)
-            self.dmub = torch.zeros((T, B, Zp), device=dev, dtype=torch.bfloat16)
-            self.dlvb = torch.zeros((T, B, Zp), device=dev, dtype=torch.bfloat16)
-            self.da2b, self.da1b = eb(T, B, R2), eb(T, B, R1)
-        else:
-            self.dm = e(T, B, W2)
-            self.dd2, self.dd1 = e(T, B, G2), e(T, B, G1)
-            self.dmu, self.dlv = e(T, B, Z), e(T, B, Z)
-            self.da2, self.da1 = e(T, B, R2), e(T, B, R1)
-        self.dth_f = e(B, 6)  # (AIR-ASR: one step's STN read backward)
-        # all loop steps at once (AIR: only the LSTM chain is sequential)
-        self.dg_all = e(T, B, W2)
-        self.dz_all, self.tmp_a2_all = e(T, B, Z), e(T, B, R2)
-        self.dth_f_all, self.dth_b_all, self.dot_all = e(T, B, 6), e(T, B, 6), e(T, B)
-        self.dout = e(5, T, B, 2)
-        # heads side by side per row ([T, B, 5, HS]): dh is one GEMM over K = 5 HS;
-        # 4 HS floats of slack after it, so that head z's column view spans
-        # T*B whole rows from its origin (the grouped weight-gradient kernels
-        # read K x ld elements of an operand, mog_wgrad_tn_x3)
-        self.dhid = e(T * B * 5 * HS + 4 * HS)[:T * B * 5 * HS].view(T, B, 5, HS)
-        self.dh = e(T, B, H)
-        self.dc = e(2, B, H)
-        self.dG = e(T, B, 4 * H)
-        self.dGsum = e(B, 4 * H)
-        self._bwd = True
-
-
-class AIRModel(GlimpseVAE, WeightGradients, GraphCapture, Results):
+class AIRModel(ModelBase, Generation):
     """See module docstring.  Extra keyword-only arguments (not in the
     reference): ``device``, ``seed`` (weight init), ``noise_seed`` (device
     Philox noise), ``grad_world`` (data-parallel world size folded into the
@@ -226,151 +83,42 @@ class AIRModel(GlimpseVAE, WeightGradients, GraphCapture, Results):
                  num_prior=None, *, device=None, seed: int = 1235, noise_seed: int = 1235,
                  grad_world: int = 1, precision: str = "fp32", fused_step: bool = True,
                  batch_vae: bool = True):
-        if precision not in ("fp32", "bf16"):
-            raise ValueError("precision must be 'fp32' (bit-exact parity) or 'bf16'")
-        self.precision = precision
-        # bf16: one fused STN-read -> VAE -> STN-write launch per loop step
-        # (vae_step.hip) when the VAE has the reference's default shape
-        self.fused_step = bool(fused_step) and precision == "bf16" and (
-            windows_size == 28 and tuple(vae_recognition_units) == (512, 256)
-            and vae_latent_dimensions == 50 and tuple(vae_generative_units) == (256, 512))
-        # fp32: the same fused step at the reference precision over the T*B
-        # rows of the batched VAE (stn_vae_step_f32_kernel; fused_step=False
-        # runs the unfused sequence it is bit-identical to)
-        self.fused_f32 = bool(fused_step) and precision == "fp32" and (
-            windows_size == 28 and tuple(vae_recognition_units) == (512, 256)
-            and vae_latent_dimensions == 50 and tuple(vae_generative_units) == (256, 512))
-        # the glimpse VAE of all T steps after the loop, over T*B rows (AIR).
-        # (Measured and not kept: step 0's VAE on a second stream under the
-        # rest of the recurrent loop -- no gain at B = 8192, slower at 64.)
-        self.batch_vae = bool(batch_vae)
         if cnn:
             raise NotImplementedError(
                 "cnn=True (air_model.py:763-810) is outside the hot-path scope; the entry "
                 "points use cnn=False")
         if not (scale_hidden_units == shift_hidden_units == z_pres_hidden_units):
             raise NotImplementedError("heads must share one hidden width")
-        self.device = torch.device(device) if device is not None else torch.device("cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("AIRModel runs on a HIP device only (no CPU fallback)")
-        _lib.load_torch_ops()
-        self.input_images = input_images
-        self.target_num_digits = target_num_digits
-        self.max_steps, self.max_digits = int(max_steps), max_digits
-        self.rnn_units = int(rnn_units)
-        self.canvas_size, self.windows_size = int(canvas_size), int(windows_size)
-        self.C2, self.W2 = self.canvas_size ** 2, self.windows_size ** 2
-        self.vae_latent_dimensions = int(vae_latent_dimensions)
-        self.vae_recognition_units = tuple(vae_recognition_units)
-        self.vae_generative_units = tuple(vae_generative_units)
-        self.scale_prior_mean, self.scale_prior_variance = scale_prior_mean, scale_prior_variance
-        self.shift_prior_mean, self.shift_prior_variance = shift_prior_mean, shift_prior_variance
-        self.vae_prior_mean, self.vae_prior_variance = vae_prior_mean, vae_prior_variance
-        self.vae_likelihood_std = vae_likelihood_std
-        self.scale_hidden_units = scale_hidden_units
-        self.shift_hidden_units = shift_hidden_units
-        self.z_pres_hidden_units = z_pres_hidden_units
-        self.z_pres_prior_log_odds = z_pres_prior_log_odds
-        self.z_pres_temperature = z_pres_temperature
-        self.stopping_threshold = stopping_threshold
-        self.learning_rate = learning_rate
-        self.gradient_clipping_norm = gradient_clipping_norm
-        self.num_summary_images = num_summary_images
-        self.train = bool(train)
-        self.scope = scope
-        self.annealing_schedules = dict(annealing_schedules or {})
-        self.generation_batch_size = generation_batch_size
+        super().__init__(
+            input_images=input_images, target_num_digits=target_num_digits, max_steps=max_steps,
+            max_digits=max_digits, rnn_units=rnn_units, canvas_size=canvas_size,
+            windows_size=windows_size, vae_latent_dimensions=vae_latent_dimensions,
+            vae_recognition_units=vae_recognition_units, vae_generative_units=vae_generative_units,
+            scale_prior_mean=scale_prior_mean, scale_prior_variance=scale_prior_variance,
+            shift_prior_mean=shift_prior_mean, shift_prior_variance=shift_prior_variance,
+            vae_prior_mean=vae_prior_mean, vae_prior_variance=vae_prior_variance,
+            vae_likelihood_std=vae_likelihood_std, scale_hidden_units=scale_hidden_units,
+            shift_hidden_units=shift_hidden_units, z_pres_hidden_units=z_pres_hidden_units,
+            z_pres_prior_log_odds=z_pres_prior_log_odds, z_pres_temperature=z_pres_temperature,
+            stopping_threshold=stopping_threshold, learning_rate=learning_rate,
+            gradient_clipping_norm=gradient_clipping_norm, num_summary_images=num_summary_images,
+            train=train, scope=scope, annealing_schedules=annealing_schedules,
+            generation_batch_size=generation_batch_size, device=device, noise_seed=noise_seed,
+            grad_world=grad_world, precision=precision, fused_step=fused_step)
+        # the glimpse VAE of all T steps after the loop, over T*B rows.
+        # (Measured and not kept: step 0's VAE on a second stream under the
+        # rest of the recurrent loop -- no gain at B = 8192, slower at 64.)
+        self.batch_vae = bool(batch_vae)
         self.num_prior = num_prior
-        self.noise_seed = int(noise_seed)
-        self.grad_world = int(grad_world)
-        self._noise_ctr = 0
-        self.scale_prior_log_variance = _f32log(scale_prior_variance)
-        self.shift_prior_log_variance = _f32log(shift_prior_variance)
-        self.vae_prior_log_variance = _f32log(vae_prior_variance)
-        self.marginal = (marginal_objective(num_prior, self.max_steps)
-                         if num_prior is not None else None)
-        specs = param_specs(self.C2, self.rnn_units, self.W2, self.vae_recognition_units,
-                            self.vae_generative_units, self.vae_latent_dimensions,
-                            scale_hidden_units, z_pres_hidden_units)
-        if reuse:
-            if scope not in _SCOPES:
-                raise ValueError(f"reuse=True but scope {scope!r} has no variables yet")
-            self.params = _SCOPES[scope]
-            if self.params.specs != specs:
-                raise ValueError("reused scope has different variable shapes")
-        else:
-            self.params = ParamStore(specs, self.device, seed=seed)
-            _SCOPES[scope] = self.params
-        self._ws: Optional[_Workspace] = None
-        self._last_T = None
-        self._outputs_ready = False
+        if num_prior is not None:
+            self.marginal = marginal_objective(num_prior, self.max_steps)
+        self._bind_params(scope, param_specs(
+            self.C2, self.rnn_units, self.W2, self.vae_recognition_units,
+            self.vae_generative_units, self.vae_latent_dimensions, scale_hidden_units,
+            z_pres_hidden_units), reuse, seed)
 
-    # ----------------------------------------------------------- helpers ---
-    # Optional per-kernel HIP-event timing (bench.py roofline): when
-    # ``kernel_events`` is a dict, every tagged launch records (start, end,
-    # work, side) on the stream it is launched on; work = (bound, amount,
-    # peak[, "x3"]) -- algorithmic flops ("mfma", peak "fp32" / "bf16"; "x3":
-    # fp32 flops issued as six bf16 products) or bytes ("hbm") of that one
-    # launch, or None (bench.kernel_work prices the tag); side: launched on
-    # one of the shared side streams.
-    kernel_events = None
-
-    class _NoTimer:
-        def __enter__(self):
-            return self
-
-        def __exit__(self, *a):
-            return False
-
-    class _Timer:
-        def __init__(self, sink, name, work):
-            self.sink, self.name, self.work = sink, name, work
-
-        def __enter__(self):
-            self.e0 = torch.cuda.Event(enable_timing=True)
-            self.e1 = torch.cuda.Event(enable_timing=True)
-            s = torch.cuda.current_stream()
-            self.e0.record(s)
-            # a launch on a side stream: its events also count the time its
-            # first workgroups wait for CUs the main stream's kernels hold
-            self.side = any(s == o for o in _STREAMS.get(s.device, ()))
-            return self
-
-        def __exit__(self, *a):
-            self.e1.record(torch.cuda.current_stream())
-            self.sink.setdefault(self.name, []).append((self.e0, self.e1, self.work, self.side))
-            return False
-
-    def _timed(self, name, work=None):
-        if self.kernel_events is None:
-            return AIRModel._NoTimer()
-        return AIRModel._Timer(self.kernel_events, name, work)
-
-    @property
-    def global_step(self) -> int:
-        return self.params.global_step
-
-    # Data parallelism (parallel.attach): the loss is the mean over the GLOBAL
-    # batch, so each rank scales its loss gradient by 1/B_global and the SUM
-    # all-reduce of the shards' gradients is the full-batch gradient even for
-    # unequal shards.  B_global defaults to B_local * grad_world; the trainer
-    # passes the true global batch of each step (global_batch=...).
-    _global_batch: Optional[int] = None
-
-    def _gscale(self, B: int) -> float:
-        gb = self._global_batch if self._global_batch is not None else B * self.grad_world
-        return 1.0 / float(gb)
-
-    # set by parallel.attach: bucketed async SUM all-reduce of params.grad
-    # (launch(view) as buckets become final during the backward, wait() before
-    # the optimizer) and, for the data-dependent loop exit, a MAX all-reduce of
-    # each step's live flag (only where the exit changes the loss: ``-ap``)
-    grad_reducer = None
-    live_hook = None
-
-    def _reduce_bucket(self, lo: int, hi: int) -> None:
-        if self.grad_reducer is not None:
-            self.grad_reducer.launch(self.params.grad[lo:hi])
+    _HEADS = ("scale/mean", "scale/log_variance", "shift/mean", "shift/log_variance",
+              "z_pres/log_odds")
 
     def _bucket_split(self) -> int:
         """Flat offset where the glimpse-side variables (heads, VAE) start:
@@ -378,81 +126,6 @@ class AIRModel(GlimpseVAE, WeightGradients, GraphCapture, Results):
         (params.param_specs order)."""
         return self.params.offsets[self._SCOPE_PREFIX + "scale/mean/hidden/weights"]
 
-    def hyper(self, name: str) -> float:
-        """Current value of a possibly-annealed hyper-parameter, evaluated at
-        the pre-increment global step (as in the reference forward pass)."""
-        if name in self.annealing_schedules:
-            return annealed_value(self.annealing_schedules[name], self.params.global_step)
-        return float(getattr(self, name))
-
-    def _workspace(self, B: int) -> _Workspace:
-        if self._ws is None or self._ws.B != B:
-            self._ws = _Workspace(self, B)
-        return self._ws
-
-    _SCOPE_PREFIX = "air/rnn/"  # variable scope of the loop body (air_model.py:127,812)
-
-    def _P(self, name):
-        return self.params.view(self._SCOPE_PREFIX + name)
-
-    def _G(self, name):
-        return self.params.g(self._SCOPE_PREFIX + name)
-
-    _HEADS = ("scale/mean", "scale/log_variance", "shift/mean", "shift/log_variance",
-              "z_pres/log_odds")
-
-    def _fill_noise(self, ws: _Workspace, noise: Optional[Dict[str, torch.Tensor]]):
-        ws.eps_x_offset = None  # injected noise: every consumer reads the buffers
-        ws.noise_side = False
-        if noise is not None:
-            for k in ("eps_scale", "eps_shift", "eps_z", "eps_x", "u"):
-                src = noise[k]
-                dst = getattr(ws, k)
-                if tuple(src.shape) != tuple(dst.shape):
-                    raise ValueError(f"noise[{k}] has shape {tuple(src.shape)}, "
-                                     f"expected {tuple(dst.shape)}")
-                dst.copy_(src)
-            return
-        side = None
-        if self.NOISE_ON_SIDE and ws.B >= self.SIDE_MIN_BATCH:
-            # on the side stream, under the x-projection (which needs none of
-            # it); _forward joins it after that GEMM
-            side = self._fork(self._side_stream())
-        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-            # the step's noise buffers in one launch, each with its own Philox
-            # counter range (bit-identical to one mog_rng_fill per buffer)
-            outs, offs, nrm = [], [], []
-            for k, normal in (("eps_scale", True), ("eps_shift", True), ("eps_z", True),
-                              ("eps_x", True), ("u", False)):
-                buf = getattr(ws, k)
-                if k == "eps_x" and self._eps_x_in_kernel(ws.B) and not self._graph_noise:
-                    # generated inside the fused step kernel / the fp32 output
-                    # layer's epilogue from the same Philox counters
-                    # (bit-identical to filling the buffer)
-                    ws.eps_x_offset = self._noise_ctr
-                else:
-                    outs.append(buf)
-                    offs.append(ops._i64(self._noise_ctr))
-                    nrm.append(1 if normal else 0)
-                self._noise_ctr += (buf.numel() + 3) // 4
-            _ops.rng_fill_batch_(outs, ops._i64(self.noise_seed), offs, nrm)
-        ws.noise_side = side is not None
-
-    def _reset_loop_state(self, ws):
-        """tf.while_loop's initial state (air_model.py:815-826): stopping sum,
-        running loss, counts 0, live flags 1 for step 0 and 0 after (and the
-        running canvas when the step does not use parts) -- one launch (a
-        fill kernel: capturable, unlike a host copy)."""
-        bufs = [ws.stop, ws.runloss, ws.digits, ws.live[:1], ws.live[1:]]
-        vals = [0, 0, 0, 1, 0]
-        if ws.cparts is None:
-            bufs.append(ws.canvas)
-            vals.append(0)
-        _ops.fill32_batch_(bufs, vals)
-
-    # AIR's _forward joins side-stream noise after the x-projection (the ASR
-    # subclass fills on the current stream)
-    NOISE_ON_SIDE = True
     # batched VAE: every step's heads and scalars in one launch each after
     # the LSTM chain (False: per step, as the unbatched loop;
     # tests/test_gpu_steps_fwd.py compares the two bitwise)
@@ -463,24 +136,17 @@ class AIRModel(GlimpseVAE, WeightGradients, GraphCapture, Results):
                  need_grad: bool, outputs: bool = True) -> None:
         B, T, H = ws.B, self.max_steps, self.rnn_units
         C, W, C2, W2 = self.canvas_size, self.windows_size, self.C2, self.W2
-        Z = self.vae_latent_dimensions
-        R1, R2 = self.vae_recognition_units
-        G1, G2 = self.vae_generative_units
         HS = self.scale_hidden_units
         K = self._P("rnn/basic_lstm_cell/kernel")
         bK = self._P("rnn/basic_lstm_cell/bias")
         Wx, Wh = K[:C2], K[C2:]
-        side = self._side_stream() if getattr(ws, "noise_side", False) else None
+        side = self._side_stream() if ws.noise_side else None
         ws.noise_side = False
         with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
             # (after the noise on the side stream, when it went there)
             self._reset_loop_state(ws)
             if need_grad and self._x3p_xgrad(B):
-                # the x-part gradient's A operand, split once per step
-                C2p = self._pad8(C2)
-                if getattr(ws, "X3", None) is None:
-                    ws.X3 = torch.empty((3, B, C2p), device=self.device, dtype=torch.bfloat16)
-                ops.split3_bf16(X, ws.X3, B, C2, C2, C2p, B * C2p)
+                self._x_split3(X, ws)  # the x-part gradient's A operand, split once per step
             if need_grad and self.precision == "bf16":
                 self._x_bf16(X, ws)  # (likewise: the bf16 x-part gradient's A operand)
             if (need_grad and self.precision == "fp32" and self.VAE_DX_X3
@@ -613,15 +279,6 @@ class AIRModel(GlimpseVAE, WeightGradients, GraphCapture, Results):
                          ws.means)
         self._outputs_ready = True
 
-    def _materialize(self):
-        """Store the canvas / reconstruction of the last forward (recomputes
-        the loss kernel once with its output pointers; same values)."""
-        ws = self._ws
-        if ws is None or ws.materialized:
-            return
-        X, targets = self._loss_inputs
-        self._forward_loss(X, targets, ws, need_grad=False, outputs=True)
-
     # ---------------------------------------------------------- backward ---
     def _backward(self, X: torch.Tensor, ws: _Workspace) -> None:
         """Every loop step's glimpse-path backward (STN write, VAE, STN read,
@@ -637,52 +294,6 @@ class AIRModel(GlimpseVAE, WeightGradients, GraphCapture, Results):
             _ops.fill32_batch_([st.grad, ws.dGsum], [0, 0])
         self._backward_body_grouped(X, ws)
 
-    def _backward_body_grouped(self, X, ws) -> None:
-        """_backward_body; small batch, one GPU: the fp32-chain weight
-        gradients it meets are collected (_dw) and run as one grouped launch
-        at the end."""
-        self._wgroup = (self._wgroup_obj if (self.WGRAD_GROUP and ws.B < self.SIDE_MIN_BATCH
-                                             and self.grad_reducer is None) else None)
-        wg = self._wgroup
-        if wg is not None:
-            wg.probs = []  # (a fresh collection: nothing left from a failed step)
-        try:
-            self._backward_body(X, ws)
-        except BaseException:
-            if wg is not None:
-                wg.probs = []  # a failed body's partial problems never launch
-            raise
-        finally:
-            self._wgroup = None
-        if wg is not None and wg.probs:
-            flops = sum(2.0 * p[4] * p[5] * p[6] for p in wg.probs)
-            with self._timed("wgrad_group", ("mfma", flops, "fp32")):
-                wg.launch()
-
-    # the grouped weight-gradient launch below SIDE_MIN_BATCH (batch 64: 11
-    # launches of a few k-steps each -> one)
-    WGRAD_GROUP = True
-    _wgroup = None
-
-    @property
-    def _wgroup_obj(self):
-        g = self.__dict__.get("_wgroup_obj_")
-        if g is None:
-            g = self.__dict__["_wgroup_obj_"] = ops.WgradGroup()
-        return g
-
-    def _stn_write_backward_all(self, ws) -> None:
-        """Every loop step's STN write backward in one launch over T*B rows
-        against the shared canvas gradient (it reads only the forward's
-        records); the glimpse cotangent leaves through the VAE's output
-        sigmoid straight from the kernel (dm fp32 / dmb bf16: bit-identical
-        to dU followed by mog_sigmoid_backward)."""
-        TB, C = self.max_steps * ws.B, self.canvas_size
-        dm = ws.dmb if self.precision == "bf16" else ws.dm
-        ops.stn_backward(ws.r.view(TB, -1), ws.th_b, (C, C), ws.dcanvas, gscale=ws.zc,
-                         dtheta=ws.dth_b_all, dot=ws.dot_all, want_dot=True, n=TB,
-                         dm=dm.view(TB, -1))
-
     def _backward_body(self, X: torch.Tensor, ws: _Workspace) -> None:
         B, T, H = ws.B, self.max_steps, self.rnn_units
         W, C2 = self.windows_size, self.C2
@@ -691,7 +302,6 @@ class AIRModel(GlimpseVAE, WeightGradients, GraphCapture, Results):
         K = self._P("rnn/basic_lstm_cell/kernel")
         bK = self._P("rnn/basic_lstm_cell/bias")
         Wh = K[C2:]
-        w1 = [self._P(h + "/hidden/weights") for h in self._HEADS]
         w2 = [self._P(h + "/output/weights") for h in self._HEADS]
         gscale = self._gscale(B)
         prior_lo = self.hyper("z_pres_prior_log_odds")
@@ -714,7 +324,10 @@ class AIRModel(GlimpseVAE, WeightGradients, GraphCapture, Results):
         # kernel runs alone, is neutral -- 3.097 / 3.094 vs 3.098 / 3.097 ms).
         # Below SIDE_MIN_BATCH everything stays on the main stream (see
         # _vae_weight_grads_async).
-        w1_done, vae_done = self._vae_weight_grads_async(ws)
+        # (from SIDE_MIN_BATCH the heads' concatenated W1, the B operand of
+        # the dh GEMM below, is refreshed first on that stream: off the main
+        # stream, which waits for it only at that GEMM)
+        w1_done, vae_done = self._vae_weight_grads_async(ws, first=self._w1cat)
         # STN read backward of all steps against the shared input canvas
         with self._timed("stn_read_bwd", self._stn_bwd_work(TB, write=False)):
             ops.stn_backward(X, ws.th_f, (W, W), ws.dg_all, want_dU=False, dtheta=ws.dth_f_all,
@@ -774,19 +387,16 @@ class AIRModel(GlimpseVAE, WeightGradients, GraphCapture, Results):
             self._reduce_bucket(split, self.params.total)
         rec_early = T > 1 and heads_side and self.REC_WGRAD_SIDE
         dGsum = None if self._x3p_xgrad(B) else ws.dGsum
-        # a small batch's dh GEMM (K = 4H walked serially by a dozen workgroups)
-        # split over K into DH_PARTS products that the next cell backward adds
-        # to the heads' dh in part order (mog_lstm_cell_backward_parts)
-        parts = self.DH_PARTS if (B < self.SIDE_MIN_BATCH and self.DH_PARTS > 1
-                                  and (4 * H) % (4 * self.DH_PARTS) == 0) else 0
-        if parts and getattr(ws, "dh_parts", None) is None:
-            ws.dh_parts = torch.empty((parts, B, H), device=self.device)
+        # a small batch's dh GEMM in DH_PARTS K slices that the next cell
+        # backward adds to the heads' dh in part order (_dh_parts)
+        parts = self._dh_parts(B)
+        dh_parts = ws.buffer("dh_parts", (parts, B, H)) if parts else None
         for t in reversed(range(T)):
             dc_in = ws.dc[(t + 1) % 2] if t < T - 1 else None
             G_t, b_t = (ws.Gx, bK) if t == 0 else (ws.G[t], None)
             c_prev = ws.c[t - 1] if t > 0 else None
             if parts and t < T - 1:
-                _ops.lstm_cell_backward_parts_(G_t, b_t, c_prev, ws.c[t], ws.dh[t], ws.dh_parts,
+                _ops.lstm_cell_backward_parts_(G_t, b_t, c_prev, ws.c[t], ws.dh[t], dh_parts,
                                                parts, dc_in, ws.dG[t], ws.dc[t % 2], dGsum, B, H)
             else:
                 _ops.lstm_cell_backward_(G_t, b_t, c_prev, ws.c[t], ws.dh[t], dc_in, ws.dG[t],
@@ -798,7 +408,7 @@ class AIRModel(GlimpseVAE, WeightGradients, GraphCapture, Results):
             if t > 0 and parts:
                 kp = 4 * H // parts
                 gemm([ws.dG[t][:, j * kp:] for j in range(parts)],
-                     [Wh[:, j * kp:] for j in range(parts)], [ws.dh_parts[j] for j in range(parts)],
+                     [Wh[:, j * kp:] for j in range(parts)], [dh_parts[j] for j in range(parts)],
                      B, H, kp, 4 * H, 4 * H, H, transB=True)
             elif t > 0:
                 gemm([ws.dG[t]], [Wh], [ws.dh[t - 1]], B, H, 4 * H, 4 * H, 4 * H, H,
@@ -812,116 +422,118 @@ class AIRModel(GlimpseVAE, WeightGradients, GraphCapture, Results):
     HEADS_WGRAD_SIDE = True
     # ... and the LSTM kernel's recurrent-rows gradient beside the x-rows one
     REC_WGRAD_SIDE = True
-    # K-split of the small-batch dh GEMM (0: one chain per output, Cin = the
-    # heads' dh)
-    DH_PARTS = 4
-    # the round-3 side-stream moves (noise + resets under the x-projection,
-    # heads' weight gradients under the LSTM chain) from this batch: below it
-    # the launches are too short to hide the cross-stream waits (batch 64:
-    # eager 0.90 -> 1.00 ms, captured 0.60 -> 0.65 ms with them)
-    SIDE_MIN_BATCH = 1024
 
-    def _stn_bwd_work(self, rows, write):
-        """Algorithmic HBM bytes of one STN backward launch over `rows` image-
-        steps: write -- r and dm (C2... of the glimpse), the
-        canvas cotangent shared by the T steps of an image, theta / dtheta /
-        dot; read -- the input canvas shared likewise, the glimpse cotangent,
-        theta / dtheta."""
-        W2, C2, T = self.W2, self.C2, self.max_steps
-        if write:
-            dm = 2 if self.precision == "bf16" else 4
-            return ("hbm", rows * (W2 * 4 + W2 * dm + C2 * 4 / T + 52), None)
-        return ("hbm", rows * (C2 * 4 / T + W2 * 4 + 48), None)
+    # -------------------------------------------------- weight gradients ---
+    # (the forms and the VAE's are WeightGradients', wgrads.py)
+    def _w1cat(self):
+        """[W1_0 .. W1_4] side by side ([H, 5 HS]): the B operand of the heads'
+        dh GEMM, refreshed when the parameters change."""
+        return self._wcache.get("w1cat", self._w1cat_build)
 
-    # the side and third streams are created once per process and device and
-    # shared by every model (see _shared_streams)
-    def _stream3(self):
-        return _shared_streams(self.device)[1]
+    def _w1cat_build(self):
+        buf = torch.empty((self.rnn_units, 5 * self.scale_hidden_units), device=self.device)
+        return buf, lambda: torch.cat([self._P(h + "/hidden/weights") for h in self._HEADS],
+                                      dim=1, out=buf)
 
-    def _side_stream(self):
-        return _shared_streams(self.device)[0]
+    def _weight_grads_heads(self, ws):
+        H, HS, TB = self.rnn_units, self.scale_hidden_units, ws.B * self.max_steps
+        heads = list(enumerate(self._HEADS))
+        dhid = ws.dhid.view(TB, 5, HS)
+        g = self._G
+        if (self._wgroup is None and TB >= self.WGRAD_TN_MIN_ROWS
+                and H % 2 == 0 and HS % 2 == 0 and HS < 128):
+            # deterministic from the split-K batch sizes on: the five hidden
+            # layers on the grouped x3 kernel (splits added in order), the 1- /
+            # 2-column output layers by chunk partials added in chunk order
+            # (mog_heads_output_wgrad)
+            flops = 2.0 * TB * H * HS * 5
+            with self._timed("heads_wgrad_x3", ("mfma", flops, "fp32", "x3")):
+                ops.wgrad_tn_x3([ws.h] * 5, [dhid[:, zi] for zi, _ in heads],
+                                [g(h + "/hidden/weights") for _, h in heads],
+                                [g(h + "/hidden/biases") for _, h in heads],
+                                [(H, HS, H, 5 * HS, HS)] * 5, TB, self.WGRAD_TN_X3_SPLITS)
+            _ops.heads_output_wgrad_([ws.hid[zi] for zi, _ in heads],
+                                     [ws.dout[zi] for zi, _ in heads],
+                                     [g(h + "/output/weights") for _, h in heads],
+                                     [g(h + "/output/biases") for _, h in heads],
+                                     [2 if h.startswith("shift") else 1 for _, h in heads], TB, HS)
+            return
+        self._dw([ws.h] * 5, [dhid[:, zi] for zi, _ in heads],
+                 [g(h + "/hidden/weights") for _, h in heads], TB, H, HS, H, 5 * HS,
+                 [g(h + "/hidden/biases") for _, h in heads])
+        for k in (1, 2):
+            sel = [(zi, h) for zi, h in heads if (2 if h.startswith("shift") else 1) == k]
+            self._dw([ws.hid[zi] for zi, _ in sel], [ws.dout[zi] for zi, _ in sel],
+                     [g(h + "/output/weights") for _, h in sel], TB, HS, k, HS, 2,
+                     [g(h + "/output/biases") for _, h in sel])
 
-    # stream-ordering test instrument (tests/test_gpu_streams.py): ticks of the
-    # 100 MHz wall clock that a spin kernel holds back the head of every forked
-    # segment (SPIN_FORK) or the main stream at the start of a step (SPIN_MAIN)
-    SPIN_FORK = 0
-    SPIN_MAIN = 0
+    def _x3p_xgrad(self, B):
+        """fp32: the LSTM kernel's x-rows gradient on the pre-split
+        three-piece form (X_GRAD_X3 = 2) from X3P_MIN_B, reading every step's
+        dG (mog_split3_sum_bf16: at most 8 steps) instead of their running
+        sum.  The forward's split of X, the backward's dGsum and
+        _weight_grads_lstm all key on this one predicate."""
+        return (self.precision == "fp32" and self.X_GRAD_X3 == 2 and B >= self.X3P_MIN_B
+                and self.max_steps <= 8)
 
-    def _fork(self, stream):
-        """Order `stream` after everything issued so far on the current
-        stream; returns it."""
-        ready = torch.cuda.Event()
-        ready.record(torch.cuda.current_stream())
-        stream.wait_event(ready)
-        if self.SPIN_FORK:
-            with torch.cuda.stream(stream):
-                ops.spin(self.SPIN_FORK)
-        return stream
+    def _weight_grads_rec_side(self, ws):
+        """One GPU: the LSTM kernel's recurrent-rows gradient sum_t h[t-1]^T
+        dG[t] on a side stream, forked as soon as dG[1:] is final (before the
+        chain's step 0), so it overlaps that step instead of the x-rows
+        gradient."""
+        # (on the third stream after the heads' weight gradients: 3.06 ->
+        # 3.04 ms against the side stream)
+        with torch.cuda.stream(self._fork(self._stream3())):
+            self._dw_rec(ws)
 
-    # ------------------------------------------------------------- API ----
-    def _prep(self, images, targets):
-        X = torch.as_tensor(images, dtype=torch.float32).to(self.device).reshape(-1, self.C2)
-        X = X.contiguous()
-        tg = None
-        if targets is not None:
-            tg = torch.as_tensor(targets).to(self.device, torch.int32).contiguous()
-        return X, tg
+    def _dw_rec(self, ws):
+        """The LSTM kernel's recurrent rows: gK[C2:] += sum_t h[t-1]^T dG[t]
+        over (T-1) B rows.  From WGRAD_TN_MIN_ROWS (either precision:
+        fp32-level, and faster than the fp32 chain): on the bf16 matrix cores
+        with exact three-piece splits (the grouped x3 kernel of the fp32 VAE
+        weight gradients, one problem, 256 x 1024 x 16,384 at B = 8192), else
+        the fp32 split-K GEMM."""
+        B, T, H, C2 = ws.B, self.max_steps, self.rnn_units, self.C2
+        gK = self._G("rnn/basic_lstm_cell/kernel")
+        K = (T - 1) * B
+        if self.REC_WGRAD_X3 and K >= self.WGRAD_TN_MIN_ROWS:
+            # the grouped x3 kernel with one problem: deterministic
+            with self._timed("rec_wgrad_x3", ("mfma", 2.0 * K * H * 4 * H, "fp32", "x3")):
+                ops.wgrad_tn_x3([ws.h], [ws.dG[1:]], [gK[C2:]], [None],
+                                [(H, 4 * H, H, 4 * H, 4 * H)], K, self.WGRAD_TN_X3_SPLITS)
+        else:
+            self._dw(ws.h, ws.dG[1:], gK[C2:], K, H, 4 * H, H, 4 * H)
 
-    def train_step_async(self, images, targets=None, noise=None,
-                         global_batch: Optional[int] = None) -> None:
-        """One train step (forward, backward, [bucketed all-reduce], clip,
-        Adam) with no host synchronisation.  ``global_batch``: images over all
-        data-parallel ranks this step (default: local batch x grad_world)."""
-        if not self.train:
-            raise RuntimeError("train_step on a model built with train=False")
-        X, tg = self._prep(images, targets)
-        ws = self._workspace(X.shape[0])
-        ws.alloc_backward(self)
-        if self.SPIN_MAIN:
-            ops.spin(self.SPIN_MAIN)
-        self._fill_noise(ws, noise)
-        self._global_batch = global_batch
-        self._forward(X, tg, ws, need_grad=True, outputs=False)
-        self._backward(X, ws)
-        if self.grad_reducer is not None:
-            self.grad_reducer.wait()
-        self.params.apply_adam(self.hyper("learning_rate"), self.gradient_clipping_norm)
-        self.params.global_step += 1
-        self._X = X
-
-    def step(self, images, targets=None, noise=None, global_batch: Optional[int] = None):
-        """``sess.run([training, loss, accuracy, mse_loss, global_step])``
-        (training_air_original.py:304-310)."""
-        self.train_step_async(images, targets, noise, global_batch)
-        m = self._ws.means.detach().cpu().numpy()
-        return float(m[0]), float(m[1]), float(m[2]), self.params.global_step
-
-    def compute_gradients(self, images, targets=None, noise=None, canvas_cotangent=None,
-                          global_batch: Optional[int] = None):
-        """Forward + backward (+ the data-parallel all-reduce when attached),
-        no optimizer update; returns the gradient dict.  ``canvas_cotangent``
-        [B, C*C] replaces dL/dcanvas of the BCE term (used by the gradient
-        parity tests)."""
-        X, tg = self._prep(images, targets)
-        ws = self._workspace(X.shape[0])
-        ws.alloc_backward(self)
-        if self.SPIN_MAIN:
-            ops.spin(self.SPIN_MAIN)
-        self._fill_noise(ws, noise)
-        self._global_batch = global_batch
-        self._forward(X, tg, ws, need_grad=True)
-        if canvas_cotangent is not None:
-            ws.dcanvas.copy_(torch.as_tensor(canvas_cotangent, dtype=torch.float32))
-        self._backward(X, ws)
-        if self.grad_reducer is not None:
-            self.grad_reducer.wait()
-        return self.params.grad_dict()
-
-    def infer(self, images, targets=None, noise=None):
-        """Forward pass only (the test model's fetches)."""
-        X, tg = self._prep(images, targets)
-        ws = self._workspace(X.shape[0])
-        self._fill_noise(ws, noise)
-        self._forward(X, tg, ws, need_grad=False)
-        self._X = X
-        return self
+    def _weight_grads_lstm(self, X, ws, side=False, rec_done=False):
+        """LSTM kernel / bias gradients.  Data parallel: the x-part X^T dGsum
+        (2500 x 1024, 10 MB) is produced in row chunks, each handed to the
+        all-reduce as soon as it is final, so the collective of chunk i runs
+        under the GEMM of chunk i+1; the recurrent rows and the bias go last.
+        rec_done: the recurrent rows were forked already (_weight_grads_rec_side)."""
+        B, T, H, C2 = ws.B, self.max_steps, self.rnn_units, self.C2
+        gK = self._G("rnn/basic_lstm_cell/kernel")
+        gbK = self._G("rnn/basic_lstm_cell/bias")
+        if rec_done:
+            pass
+        elif T > 1 and side and self.REC_WGRAD_SIDE:
+            self._weight_grads_rec_side(ws)
+        elif T > 1:
+            self._dw_rec(ws)
+        chunk = self.X_GRAD_CHUNK if self.grad_reducer is not None else C2
+        base = self.params.offsets[self._SCOPE_PREFIX + "rnn/basic_lstm_cell/kernel"]
+        x3p = self._x3p_xgrad(B)
+        if x3p:
+            # the pieces of sum_t dG_t, summed in the reversed loop's order
+            # without the running sum (mog_split3_sum_bf16)
+            _ops.split3_sum_bf16_(ws.dG, T, B * 4 * H,
+                                  ws.buffer("dG3", (3, B, 4 * H), torch.bfloat16), B, 4 * H,
+                                  4 * H, 4 * H, B * 4 * H)
+        m_last = 0
+        for m0 in range(0, C2, chunk):
+            m_last = m0
+            m1 = min(C2, m0 + chunk)
+            # bias gradient = colsum(sum_t dG_t) = colsum(dGsum), fused into chunk 0
+            self._x_rows_grad(X, ws, gK, gbK if m0 == 0 else None, m0, m1, x3p)
+            if m1 < C2:
+                self._reduce_bucket(base + m0 * 4 * H, base + m1 * 4 * H)
+        self._reduce_bucket(base + m_last * 4 * H, self._bucket_split())

@@ -25,11 +25,10 @@ from typing import Dict
 
 import torch
 
-from . import _lib, ops
-from .air_model import AIRModel as _AirBase
-from .air_model import _SCOPES, _Workspace, _f32log
+from . import ops
+from .model_base import ModelBase, _Workspace
 from .ops import EPI_RELU, EPI_STORE, gemm
-from .params import ParamStore
+from .vae import _step_rows
 
 _ops = ops._ops  # torch.ops.mog_air (csrc/torch_ops.cpp)
 
@@ -97,6 +96,10 @@ class _AsrWorkspace(_Workspace):
         self.margin = e(1)
         # hg_{-1}: the zero state the learned prior reads at step 0
         self.hg_zero = torch.zeros((B, H), device=dev, dtype=torch.float32)
+        self.x3_ready = None  # the event after X's split on the side stream (_x3_asr)
+        # this step's VAE / recurrent-rows weight gradients ran per loop step
+        self.vae_wgrads_done = self.u_wgrads_done = False
+        self.dUp = self.dUgp = None  # the K slices of a small batch's dU / dUg GEMM (DH_PARTS)
 
     def alloc_backward(self, m):
         if self._bwd:
@@ -116,13 +119,14 @@ class _AsrWorkspace(_Workspace):
         self.dss_carry = e(B, 3)
 
 
-class AIRModel(_AirBase):
+class AIRModel(ModelBase):
     """See module docstring.  Extra keyword-only arguments as the AIR model
     (device, seed, noise_seed, grad_world, precision, fused_step)."""
 
     NOISE_ON_SIDE = False  # _forward below uses the noise from its first launch
 
     _SCOPE_PREFIX = ROOT
+    _WORKSPACE = _AsrWorkspace
 
     def __init__(self, input_images=None, target_num_digits=None, max_steps=3, max_digits=2,
                  rnn_units=256, canvas_size=50, windows_size=28, vae_latent_dimensions=50,
@@ -154,46 +158,27 @@ class AIRModel(_AirBase):
         cons = list(constrains_num) if constrains_num is not None else [max_steps]
         if not 1 <= len(cons) <= 8:
             raise ValueError("1..8 allowed object counts")
-        if precision not in ("fp32", "bf16"):
-            raise ValueError("precision must be 'fp32' or 'bf16'")
-        self.precision = precision
-        self.fused_step = bool(fused_step) and precision == "bf16" and (
-            windows_size == 28 and tuple(vae_recognition_units) == (512, 256)
-            and vae_latent_dimensions == 50 and tuple(vae_generative_units) == (256, 512))
-        # fp32: the fused fp32 step kernel per loop step (AIRModel._vae_forward_all)
-        self.fused_f32 = bool(fused_step) and precision == "fp32" and (
-            windows_size == 28 and tuple(vae_recognition_units) == (512, 256)
-            and vae_latent_dimensions == 50 and tuple(vae_generative_units) == (256, 512))
-        self.device = torch.device(device) if device is not None else torch.device("cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("AIRModel runs on a HIP device only (no CPU fallback)")
-        _lib.load_torch_ops()
-        self.input_images, self.target_num_digits = input_images, target_num_digits
-        self.max_steps, self.max_digits = int(max_steps), max_digits
-        self.rnn_units = int(rnn_units)
-        self.canvas_size, self.windows_size = int(canvas_size), int(windows_size)
-        self.C2, self.W2 = self.canvas_size ** 2, self.windows_size ** 2
-        self.vae_latent_dimensions = int(vae_latent_dimensions)
-        self.vae_recognition_units = tuple(vae_recognition_units)
-        self.vae_generative_units = tuple(vae_generative_units)
+        # the scale prior is fixed (:70-72); the shift prior is generation's only
+        super().__init__(
+            input_images=input_images, target_num_digits=target_num_digits, max_steps=max_steps,
+            max_digits=max_digits, rnn_units=rnn_units, canvas_size=canvas_size,
+            windows_size=windows_size, vae_latent_dimensions=vae_latent_dimensions,
+            vae_recognition_units=vae_recognition_units, vae_generative_units=vae_generative_units,
+            scale_prior_mean=-1.0, scale_prior_variance=0.05, shift_prior_mean=0.0,
+            shift_prior_variance=1.0, vae_prior_mean=vae_prior_mean,
+            vae_prior_variance=vae_prior_variance, vae_likelihood_std=vae_likelihood_std,
+            scale_hidden_units=64, shift_hidden_units=64, z_pres_hidden_units=64,
+            z_pres_prior_log_odds=z_pres_prior_log_odds, z_pres_temperature=z_pres_temperature,
+            stopping_threshold=stopping_threshold, learning_rate=learning_rate,
+            gradient_clipping_norm=gradient_clipping_norm, num_summary_images=num_summary_images,
+            train=train, scope=scope, annealing_schedules=annealing_schedules,
+            generation_batch_size=generation_batch_size, device=device, noise_seed=noise_seed,
+            grad_world=grad_world, precision=precision, fused_step=fused_step)
         self.fix_scale_distribution = True
-        self.scale_prior_mean, self.scale_prior_variance = -1.0, 0.05  # :70-72
-        self.shift_prior_mean, self.shift_prior_variance = 0.0, 1.0    # generation only
-        self.vae_prior_mean, self.vae_prior_variance = vae_prior_mean, vae_prior_variance
-        self.vae_likelihood_std = vae_likelihood_std
-        self.scale_hidden_units = self.shift_hidden_units = self.z_pres_hidden_units = 64
-        self.z_pres_prior_log_odds = z_pres_prior_log_odds
-        self.z_pres_temperature = z_pres_temperature
-        self.stopping_threshold = stopping_threshold
-        self.learning_rate = learning_rate
-        self.gradient_clipping_norm = gradient_clipping_norm
-        self.num_summary_images = num_summary_images
-        self.train = bool(train)
-        self.scope = scope
-        self.annealing_schedules = dict(annealing_schedules or {})
-        self.generation_batch_size = generation_batch_size
         self.fix_steps = fix_steps
+        self._fix = -1 if fix_steps is None else int(fix_steps)  # (the kernels' form)
         self.constrains_num = cons
+        self._cons = [int(c) for c in cons]
         self.constrains_num_gamma = constrains_num_gamma
         self.constrains_margin_gamma = constrains_margin_gamma
         self.constrains_num_element_gamma = constrains_num_element_gamma
@@ -201,47 +186,17 @@ class AIRModel(_AirBase):
         self.constrains_sharesize_gamma = constrains_sharesize_gamma
         self.constrains_area_gamma = constrains_area_gamma
         self.constrains_area_minmax = tuple(float(v) for v in constrains_area_minmax)
-        self.num_prior = None
-        self.marginal = None
-        self.noise_seed = int(noise_seed)
-        self.grad_world = int(grad_world)
-        self._noise_ctr = 0
-        self.scale_prior_log_variance = _f32log(self.scale_prior_variance)
-        self.shift_prior_log_variance = _f32log(self.shift_prior_variance)
-        self.vae_prior_log_variance = _f32log(vae_prior_variance)
-        specs = asr_param_specs(self.C2, self.rnn_units, self.W2, self.vae_recognition_units,
-                                self.vae_generative_units, self.vae_latent_dimensions, 64, 64)
-        key = "asr:" + scope
-        if reuse:
-            if key not in _SCOPES:
-                raise ValueError(f"reuse=True but scope {scope!r} has no variables yet")
-            self.params = _SCOPES[key]
-            if self.params.specs != specs:
-                raise ValueError("reused scope has different variable shapes")
-        else:
-            # the LSTM GEMMs run over LU = 312 packed rows (16-byte operand
-            # rows): 3 zero rows behind each LSTM kernel are the rows past its
-            # Z + 3 + H, so no launch reads or accumulates into a neighbour
-            kpad = (LU - (self.vae_latent_dimensions + 3 + self.rnn_units)) * 4 * self.rnn_units
-            self.params = ParamStore(specs, self.device, seed=seed,
-                                     pad={ROOT + "infer_rnn_running/kernel": kpad,
-                                          ROOT + "gen_rnn_running/kernel": kpad})
-            _SCOPES[key] = self.params
-        self._ws = None
-        self._last_T = None
-        self._outputs_ready = False
-        self._cons = [int(c) for c in cons]
+        # the LSTM GEMMs run over LU = 312 packed rows (16-byte operand
+        # rows): 3 zero rows behind each LSTM kernel are the rows past its
+        # Z + 3 + H, so no launch reads or accumulates into a neighbour
+        kpad = (LU - (self.vae_latent_dimensions + 3 + self.rnn_units)) * 4 * self.rnn_units
+        self._bind_params("asr:" + scope, asr_param_specs(
+            self.C2, self.rnn_units, self.W2, self.vae_recognition_units,
+            self.vae_generative_units, self.vae_latent_dimensions, 64, 64), reuse, seed,
+            pad={ROOT + "infer_rnn_running/kernel": kpad, ROOT + "gen_rnn_running/kernel": kpad})
 
     # zsum_hook / live_hook: data-parallel collectives (parallel.attach)
     zsum_hook = None
-
-    def _workspace(self, B):
-        if self._ws is None or self._ws.B != B:
-            self._ws = _AsrWorkspace(self, B)
-        return self._ws
-
-    def _N(self, name):
-        return self.params.view(ROOT + name)
 
     def _Kpad(self, name, buf="flat"):
         """An LSTM kernel with its zero pad rows: [rows + pad, 4H] (the GEMMs
@@ -258,9 +213,6 @@ class AIRModel(_AirBase):
         self.params._views[key] = (t, v)
         return v
 
-    def _Ng(self, name):
-        return self.params.g(ROOT + name)
-
     _OUT_W = ("inf_shift/dense_1", "inf_shift/dense_3", "inf_scale/dense", "inf_scale/dense_1",
               "inf_scale/dense_2", "inf_scale/dense_3", "gen_shift/dense_1", "gen_shift/dense_3",
               "z_pres/prior/dense_1", "z_pres/log_odds/dense_1")
@@ -268,7 +220,7 @@ class AIRModel(_AirBase):
     def _w20(self):
         ts = []
         for n in self._OUT_W:
-            ts += [self._N(n + "/kernel"), self._N(n + "/bias")]
+            ts += [self._P(n + "/kernel"), self._P(n + "/bias")]
         return ts
 
     def _gammas(self):
@@ -278,25 +230,10 @@ class AIRModel(_AirBase):
             self.hyper("constrains_sharesize_gamma"), self.hyper("constrains_area_gamma"),
             self.constrains_area_minmax[0], self.constrains_area_minmax[1])]
 
-    def _fill_noise(self, ws, noise):
-        """eps_shift [T,B,2], eps_scale [T,B], eps_z, eps_x, u (injected or
-        device Philox; the fused kernel generates eps_x itself)."""
-        if noise is not None:
-            for k in ("eps_shift", "eps_scale", "eps_z", "eps_x", "u"):
-                dst = ws.eps_scale if k == "eps_scale" else getattr(ws, k)
-                src = torch.as_tensor(noise[k], dtype=torch.float32)
-                if tuple(src.shape) != tuple(dst.shape):
-                    raise ValueError(f"noise[{k}] has shape {tuple(src.shape)}, expected "
-                                     f"{tuple(dst.shape)}")
-                dst.copy_(src)
-            ws.eps_x_offset = None
-            return
-        super()._fill_noise(ws, None)
-
     # ---------------------------------------------------------- forward ---
     def _f32_parts(self, B: int) -> bool:
         """fp32 with B >= FUSED_F32_MIN_ROWS: each step's VAE is the fused fp32
-        step kernel over that step's rows (AIRModel._vae_forward_all), writing
+        step kernel over that step's rows (GlimpseVAE._vae_forward_all), writing
         the step's canvas part (summed in step order by the loss kernel: the
         running canvas bit for bit).  Smaller batches keep the per-step
         launches (the fused kernel would leave most CUs idle, and the extra
@@ -323,24 +260,21 @@ class AIRModel(_AirBase):
         C, W, C2 = self.canvas_size, self.windows_size, self.C2
         Ki = self._Kpad("infer_rnn_running/kernel")
         Kg = self._Kpad("gen_rnn_running/kernel")
-        bi, bg = self._N("infer_rnn_running/bias"), self._N("gen_rnn_running/bias")
+        bi, bg = self._P("infer_rnn_running/bias"), self._P("gen_rnn_running/bias")
         self._reset_loop_state(ws)
         thr = self.hyper("stopping_threshold")
         temp = self.hyper("z_pres_temperature")
         lik_std = float(self.hyper("vae_likelihood_std"))
-        fix = -1 if self.fix_steps is None else int(self.fix_steps)
+        fix = self._fix
         w20 = self._w20()
         x3 = need_grad and self._x3_asr(B)
         if x3:
             # the x-rows gradient's A operand split into three bf16 pieces on
-            # the side stream, under the x-projection (AIRModel._forward does
+            # the side stream, under the x-projection (the AIR model's _forward does
             # the same); joined in _weight_grads
             side = self._fork(self._side_stream())
             with torch.cuda.stream(side):
-                C2p = self._pad8(C2)
-                if getattr(ws, "X3", None) is None:
-                    ws.X3 = torch.empty((3, B, C2p), device=self.device, dtype=torch.bfloat16)
-                ops.split3_bf16(X, ws.X3, B, C2, C2, C2p, B * C2p)
+                self._x_split3(X, ws)
                 ws.x3_ready = torch.cuda.Event()
                 ws.x3_ready.record(side)
         elif need_grad and self.precision == "bf16" and B >= self.SIDE_MIN_BATCH:
@@ -352,13 +286,13 @@ class AIRModel(_AirBase):
         # loop-invariant x-projection of the inference LSTM (chain over x first)
         with self._timed("lstm_x_projection"):
             gemm([X], [Ki[:C2]], [ws.Gx], B, 4 * H, C2, C2, 4 * H, 4 * H)
-        relu_w = [self._N(n + "/kernel") for n in ("inf_shift/dense", "inf_shift/dense_2",
+        relu_w = [self._P(n + "/kernel") for n in ("inf_shift/dense", "inf_shift/dense_2",
                                                    "z_pres/log_odds/dense")]
-        relu_b = [self._N(n + "/bias") for n in ("inf_shift/dense", "inf_shift/dense_2",
+        relu_b = [self._P(n + "/bias") for n in ("inf_shift/dense", "inf_shift/dense_2",
                                                  "z_pres/log_odds/dense")]
-        gen_w = [self._N(n + "/kernel") for n in ("gen_shift/dense", "gen_shift/dense_2")]
-        gen_b = [self._N(n + "/bias") for n in ("gen_shift/dense", "gen_shift/dense_2")]
-        sc_w = [self._N("inf_scale/dense/kernel")[:H], self._N("inf_scale/dense_2/kernel")[:H]]
+        gen_w = [self._P(n + "/kernel") for n in ("gen_shift/dense", "gen_shift/dense_2")]
+        gen_b = [self._P(n + "/bias") for n in ("gen_shift/dense", "gen_shift/dense_2")]
+        sc_w = [self._P("inf_scale/dense/kernel")[:H], self._P("inf_scale/dense_2/kernel")[:H]]
         defer = self.precision == "fp32" and self.DEFER_DECODER
         for t in range(T):
             prev = t > 0
@@ -386,8 +320,8 @@ class AIRModel(_AirBase):
             rb = list(relu_b) + list(gen_b)
             if fix < 0:
                 ra.append(ws.hg[t - 1] if prev else ws.hg_zero)
-                rw.append(self._N("z_pres/prior/dense/kernel"))
-                rb.append(self._N("z_pres/prior/dense/bias"))
+                rw.append(self._P("z_pres/prior/dense/kernel"))
+                rb.append(self._P("z_pres/prior/dense/bias"))
             gemm(ra, rw, hid[0:len(ra)], B, 64, H, H, 64, 64, epi=EPI_RELU, bias=rb)
             gemm([ws.h[t]] * 2, sc_w, hid[6:8], B, 64, H, H, 64, 64, epi=EPI_STORE)
             hid_l = [x if (k != 5 or fix < 0) else None for k, x in enumerate(hid)]
@@ -463,16 +397,15 @@ class AIRModel(_AirBase):
         _ops.fill32_batch_([self.params.grad, ws.dh, ws.dhg, ws.dGsum, ws.dGgsum], [0] * 5)
         Ki = self._Kpad("infer_rnn_running/kernel")
         Kg = self._Kpad("gen_rnn_running/kernel")
-        KU = Z + 3 + H
         gscale = self._gscale(B)
-        fix = -1 if self.fix_steps is None else int(self.fix_steps)
+        fix = self._fix
         w20 = self._w20()
         _ops.asr_terms_backward_(B, T, self.canvas_size, self._cons, self._gammas(), float(gscale),
                                  float(gscale), ws.arec, ws.live, ws.zsum, ws.dreg)
-        head_w = [self._N(n + "/kernel")[:H] for n in ("inf_shift/dense", "inf_shift/dense_2",
+        head_w = [self._P(n + "/kernel")[:H] for n in ("inf_shift/dense", "inf_shift/dense_2",
                                                      "z_pres/log_odds/dense", "inf_scale/dense",
                                                      "inf_scale/dense_2")]
-        gen_w = [self._N(n + "/kernel") for n in ("gen_shift/dense", "gen_shift/dense_2")]
+        gen_w = [self._P(n + "/kernel") for n in ("gen_shift/dense", "gen_shift/dense_2")]
         steps_side = (self.VAE_WGRAD_PER_STEP and self.grad_reducer is None
                       and B >= self.SIDE_MIN_BATCH)
         side = self._side_stream() if steps_side else None
@@ -488,22 +421,17 @@ class AIRModel(_AirBase):
         # the encoder half per step
         self._vae_decoder_backward(ws, 0, T)
         # a small batch's recurrent-input gradient in DH_PARTS K slices
-        # (AIRModel.DH_PARTS: the serial K = 4H chain per workgroup cut)
-        parts = self.DH_PARTS if (B < self.SIDE_MIN_BATCH and self.DH_PARTS > 1
-                                  and (4 * H) % (4 * self.DH_PARTS) == 0) else 0
-        if parts and getattr(ws, "dUp", None) is None:
-            ws.dUp = torch.empty((parts,) + tuple(ws.dU.shape), device=self.device)
-            ws.dUgp = torch.empty((parts,) + tuple(ws.dUg.shape), device=self.device)
+        # (_dh_parts: the serial K = 4H chain per workgroup cut)
+        parts = self._dh_parts(B)
+        if parts:
+            dUp, dUgp = ws.buffer("dUp", (parts, B, LU)), ws.buffer("dUgp", (parts, B, LU))
         for t in reversed(range(T)):
             self._vae_encoder_backward(ws, t, t + 1, gscale)
             if steps_side:
                 # step t's VAE weight gradients are final: accumulate them on
                 # the side stream under the rest of the loop
                 with torch.cuda.stream(self._fork(side)):
-                    if self.precision == "bf16":
-                        self._vae_weight_grads_bf16(ws, t)
-                    else:
-                        self._vae_weight_grads_fp32(ws, t)
+                    self._vae_weight_grads(ws, t)
             ops.stn_backward(X, ws.th_f[t], (W, W), ws.dg_all[t], want_dU=False, dtheta=ws.dth_f)
             hid = [ws.hid8[k, t] for k in range(8)]
             dpre = [ws.dpre[k, t] for k in range(8)]
@@ -522,7 +450,7 @@ class AIRModel(_AirBase):
             probs = [([dpre[k] for k in (0, 1, 2, 6, 7)], head_w, ws.dh[t], ws.dh[t]),
                      ([dpre[3], dpre[4]], gen_w, ws.dhg[t], ws.dhg[t])]
             if fix < 0 and t > 0:
-                probs.append(([dpre[5]], [self._N("z_pres/prior/dense/kernel")], ws.dhg[t - 1],
+                probs.append(([dpre[5]], [self._P("z_pres/prior/dense/kernel")], ws.dhg[t - 1],
                               ws.dhg[t - 1]))
             ops.gemm_kseg_group(probs, B, H, 64, 64, 64, H, transB=True)
             dc_in = ws.dc[(t + 1) % 2] if t < T - 1 else None
@@ -544,9 +472,9 @@ class AIRModel(_AirBase):
                      + [ws.dGg[t][:, j * kp:] for j in range(parts)],
                      [Ki[C2:][:, j * kp:] for j in range(parts)]
                      + [Kg[:, j * kp:] for j in range(parts)],
-                     [ws.dUp[j] for j in range(parts)] + [ws.dUgp[j] for j in range(parts)],
+                     [dUp[j] for j in range(parts)] + [dUgp[j] for j in range(parts)],
                      B, LU, kp, 4 * H, 4 * H, LU, transB=True)
-                _ops.asr_unpack_parts_(B, Z, H, LU, ws.dUp, ws.dUgp, parts, ws.dz_all[t - 1],
+                _ops.asr_unpack_parts_(B, Z, H, LU, dUp, dUgp, parts, ws.dz_all[t - 1],
                                        ws.dss_carry, ws.dh[t - 1], ws.dhg[t - 1], 1)
             elif t > 0:
                 # N = LU: the 3 pad columns of dU / dUg are scratch (unpack skips them)
@@ -567,7 +495,7 @@ class AIRModel(_AirBase):
         or loop step t's B rows, accumulated)."""
         B, T, H = ws.B, self.max_steps, self.rnn_units
         K = B if t is not None else B * T
-        v = (lambda x: x[t]) if t is not None else (lambda x: x)  # noqa: E731
+        v = _step_rows(T, t)
         gKi = self._Kpad("infer_rnn_running/kernel", "grad")
         gKg = self._Kpad("gen_rnn_running/kernel", "grad")
         if self.REC_WGRAD_X3 and K >= self.WGRAD_TN_MIN_ROWS:
@@ -575,12 +503,12 @@ class AIRModel(_AirBase):
             # AIRModel._dw_rec): 312 x 1024 x K each, deterministic
             with self._timed("rec_wgrad_x3", ("mfma", 2 * 2.0 * K * LU * 4 * H, "fp32", "x3")):
                 ops.wgrad_tn_x3([v(ws.U), v(ws.Ug)], [v(ws.dG), v(ws.dGg)],
-                                [gKi[self.C2:], gKg], [None, self._Ng("gen_rnn_running/bias")],
+                                [gKi[self.C2:], gKg], [None, self._G("gen_rnn_running/bias")],
                                 [(LU, 4 * H, LU, 4 * H, 4 * H)] * 2, K, self.WGRAD_TN_X3_SPLITS)
             return
         self._dw(v(ws.U), v(ws.dG), gKi[self.C2:], K, LU, 4 * H, LU, 4 * H)
         self._dw(v(ws.Ug), v(ws.dGg), gKg, K, LU, 4 * H, LU, 4 * H,
-                 self._Ng("gen_rnn_running/bias"))
+                 self._G("gen_rnn_running/bias"))
 
     # (with VAE_WGRAD_PER_STEP) the recurrent-rows gradients per step too (9.20 ->
     # 8.96 ms; the heads' gradients per step as well measured neutral, 9.01 vs
@@ -594,50 +522,31 @@ class AIRModel(_AirBase):
     VAE_WGRAD_PER_STEP = True
 
     def _weight_grads(self, X, ws):
-        B, T, H, Z = ws.B, self.max_steps, self.rnn_units, self.vae_latent_dimensions
-        C2, TB, KU = self.C2, ws.B * self.max_steps, Z + 3 + H
-        fix = -1 if self.fix_steps is None else int(self.fix_steps)
-        heads_s3 = getattr(ws, "vae_wgrads_done", False) and self.HEADS_S3
+        B, H, C2 = ws.B, self.rnn_units, self.C2
+        heads_s3 = ws.vae_wgrads_done and self.HEADS_S3
         if heads_s3:
             # the heads' weight gradients on the third stream, beside the
             # x-rows gradient (main) and step 0's on the side stream
             with torch.cuda.stream(self._fork(self._stream3())):
                 self._heads_wgrad(ws, None)
-        if getattr(ws, "vae_wgrads_done", False):
-            pass  # (per loop step, on the side stream)
-        elif self.precision == "bf16":
-            self._vae_weight_grads_bf16(ws)
-        else:
-            self._vae_weight_grads_fp32(ws)
+        if not ws.vae_wgrads_done:  # (else per loop step, on the side stream)
+            self._vae_weight_grads(ws)
         ws.vae_wgrads_done = False
-        G = self._Ng
-        gKi = self._Kpad("infer_rnn_running/kernel", "grad")
-        gKg = self._Kpad("gen_rnn_running/kernel", "grad")
         # LSTMCells: x rows from sum_t dG (the x input is loop-invariant)
-        if self.precision == "bf16":
-            self._x_grad_bf16(X, ws, gKi, G("infer_rnn_running/bias"), 0, C2)
-        elif getattr(ws, "x3_ready", None) is not None:
-            # X^T dGsum on the bf16 matrix cores from exact three-piece
-            # splits of both operands (gemm_x3.hip): the
-            # AIR x-rows gradient's form
+        x3p = ws.x3_ready is not None
+        if x3p:
+            # the AIR x-rows gradient's pre-split form: X's pieces from the
+            # forward's side stream, dGsum's split here
             torch.cuda.current_stream().wait_event(ws.x3_ready)
             ws.x3_ready = None
-            if getattr(ws, "dG3", None) is None:
-                ws.dG3 = torch.empty((3, B, 4 * H), device=self.device, dtype=torch.bfloat16)
-            ops.split3_bf16(ws.dGsum, ws.dG3, B, 4 * H, 4 * H, 4 * H, B * 4 * H)
-            C2p = self._pad8(C2)
-            with self._timed("lstm_x_projection_grad", ("mfma", 2.0 * B * C2 * 4 * H, "fp32", "x3")):
-                ops.gemm_x3p_tn(ws.X3.view(-1), B * C2p, ws.dG3, B * 4 * H, gKi[:C2], C2, 4 * H,
-                                B, C2p, 4 * H, 4 * H,
-                                splitk=self._sk(max(1, min(B // 256, self.X3_SPLITK))),
-                                colsum=G("infer_rnn_running/bias"))
-        else:
-            self._dw(X, ws.dGsum, gKi[:C2], B, C2, 4 * H, C2, 4 * H,
-                     G("infer_rnn_running/bias"))
+            ops.split3_bf16(ws.dGsum, ws.buffer("dG3", (3, B, 4 * H), torch.bfloat16), B, 4 * H,
+                            4 * H, 4 * H, B * 4 * H)
+        self._x_rows_grad(X, ws, self._Kpad("infer_rnn_running/kernel", "grad"),
+                          self._G("infer_rnn_running/bias"), 0, C2, x3p)
         # M = LU (16-byte aligned LDS-DMA operands): rows Z+3+H.. of the
         # product land in the kernels' own pad rows (ParamStore pad), never in
         # a neighbouring variable's gradient
-        if not getattr(ws, "u_wgrads_done", False):
+        if not ws.u_wgrads_done:
             self._u_rows_wgrad(ws, None)
         ws.u_wgrads_done = False
         if heads_s3:
@@ -653,9 +562,9 @@ class AIRModel(_AirBase):
         accumulated)."""
         B, T, H, Z = ws.B, self.max_steps, self.rnn_units, self.vae_latent_dimensions
         K = B if t is not None else B * T
-        v = (lambda x: x[t]) if t is not None else (lambda x: x)  # noqa: E731
-        G = self._Ng
-        fix = -1 if self.fix_steps is None else int(self.fix_steps)
+        v = _step_rows(T, t)
+        G = self._G
+        fix = self._fix
         # hidden layers reading h_t, hg_t, hg_{t-1}
         hs = ("inf_shift/dense", "inf_shift/dense_2", "z_pres/log_odds/dense", "inf_scale/dense",
               "inf_scale/dense_2")
@@ -696,14 +605,6 @@ class AIRModel(_AirBase):
                  [G(n + "/kernel")[64:] for n, _, _ in scl], K, 2, 1, 3, D_N)
 
     # ------------------------------------------------------- outputs -----
-    @property
-    def rec_scales(self):
-        return self._bt(self._ws.scale).unsqueeze(-1)
-
-    @property
-    def z_pres_probs(self):
-        return self._bt(self._ws.zprob)
-
     def _records(self, name):
         return self._bt(self._ws.arec[:, Q[name]])
 

@@ -1,4 +1,4 @@
-"""Graph capture of the AIR train step (AIRModel mixes this in): the forward
+"""Graph capture of the train step (ModelBase mixes this in): the forward
 + backward replayed from one hipGraph (torch.cuda.CUDAGraph), bit-identical
 to the eager step (tests/test_gpu_graph.py).  The reference's batch of 64
 (training_air_original.py:22) is launch-bound without it."""
@@ -106,10 +106,10 @@ class GraphCapture:
         gX = X.clone()
         gT = tg.clone() if tg is not None else None
         self._graph_io = (gX, gT)
-        # the weight packs are refreshed by a launch inside the graph on every
-        # replay (the parameters change every step): force it to be recorded
-        self._pack_version = self._pack32_version = self._w1cat_version = None
-        self._w3_version = self._vae_wT_version = None
+        # the copies derived from the weights (params.WeightCache) are refreshed
+        # by a launch inside the graph on every replay (the parameters change
+        # every step): force it to be recorded
+        self._wcache.invalidate()
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
         self._global_batch = global_batch
@@ -120,5 +120,4 @@ class GraphCapture:
         self._graph_ws = ws
         # capture executed nothing: the weight packs / copies recorded above
         # are not in their buffers yet, so the next eager use must refresh them
-        self._pack_version = self._pack32_version = self._w1cat_version = None
-        self._w3_version = self._vae_wT_version = None
+        self._wcache.invalidate()

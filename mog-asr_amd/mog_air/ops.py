@@ -254,7 +254,7 @@ def gemm_bf16(A, B, C, M: int, N: int, K: int, lda: int, ldb: int, ldc: int, tn=
 def stn_backward(U: torch.Tensor, theta: torch.Tensor, out_hw, G: torch.Tensor,
                  gscale: Optional[torch.Tensor] = None, want_dU=True, want_dtheta=True,
                  want_dot=False, dU=None, dtheta=None, dot=None, n: Optional[int] = None,
-                 dm: Optional[torch.Tensor] = None, dm_bf16: Optional[torch.Tensor] = None):
+                 dm: Optional[torch.Tensor] = None):
     """Gradient of transformer().  ``n`` images (default U's); when U or G
     holds fewer rows than ``n``, image i reads row i % rows (several loop
     steps of one batch against the shared canvas or canvas gradient).
@@ -262,11 +262,9 @@ def stn_backward(U: torch.Tensor, theta: torch.Tensor, out_hw, G: torch.Tensor,
     ``dm`` (bf16 or fp32 [N, Hin*Win], U = the VAE output sigmoid r): the
     input gradient is taken on through the sigmoid (vae.py:44-46) and stored
     there instead of dU -- bit-identical to dU followed by
-    mog_sigmoid_backward.  (``dm_bf16``: the same, kept as an alias.)"""
+    mog_sigmoid_backward."""
     _chk(U, "U")
     _chk(G, "G")
-    if dm is None:
-        dm = dm_bf16
     if U.dim() == 3:
         Hin, Win = U.shape[1], U.shape[2]
     else:

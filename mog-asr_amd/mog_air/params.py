@@ -49,6 +49,37 @@ def param_specs(C2: int, H: int, W2: int, R: Tuple[int, int], G: Tuple[int, int]
     return specs
 
 
+class WeightCache:
+    """Device buffers derived from the parameters (bf16 / fragment packs,
+    transposed or split copies): each is built once and refreshed by its own
+    launch when ``params.version`` has moved since its last refresh.  On the
+    hot path a lookup costs one dict access and one comparison."""
+
+    def __init__(self, params):
+        self._params = params
+        self._entries: Dict[str, list] = {}  # name -> [version refreshed at, value, refresh]
+
+    def get(self, name: str, build):
+        """The buffers cached under ``name``, refreshed if the parameters
+        changed.  ``build()`` runs on first use only: it allocates them and
+        returns ``(buffers, refresh)``, ``refresh()`` being the launch that
+        fills them from the current parameters (its argument lists made once,
+        in ``build``)."""
+        e = self._entries.get(name)
+        if e is None:
+            e = self._entries[name] = [None, *build()]
+        if e[0] != self._params.version:
+            e[2]()
+            e[0] = self._params.version
+        return e[1]
+
+    def invalidate(self) -> None:
+        """Forget every version: the next ``get`` of each name refreshes it (a
+        graph capture records the refresh launches without running them)."""
+        for e in self._entries.values():
+            e[0] = None
+
+
 class ParamStore:
     """Flat parameters + grads + Adam state for one scope (shared on reuse)."""
 

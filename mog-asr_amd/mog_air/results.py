@@ -1,7 +1,7 @@
-"""Generation and the result accessors of AIRModel (mixed in): the test
-model's generated_samples (air/air_model.py:1001-1146, vae.py:51-86) and the
-reference's result attributes (rec_num_digits, rec_scales, ..., sliced to the
-executed loop steps)."""
+"""Generation and the result accessors of the models (mixed in): the AIR
+test model's generated_samples (air/air_model.py:1001-1146, vae.py:51-86) and
+the reference's result attributes (rec_num_digits, rec_scales, ..., sliced to
+the executed loop steps)."""
 from __future__ import annotations
 
 from typing import Optional
@@ -14,7 +14,9 @@ from .ops import EPI_SIGMOID_NOISE, EPI_SOFTPLUS, gemm
 _ops = ops._ops
 
 
-class Results:
+class Generation:
+    """AIR's generation loop (mixed into air_model.AIRModel)."""
+
     def generate(self, num_steps: int, batch: Optional[int] = None, noise=None):
         """The test model's ``generated_samples`` (air_model.py:1001-1146):
         ``num_steps`` objects per canvas (``max_steps_generation_placeholder``),
@@ -68,7 +70,10 @@ class Results:
         self.generated_samples = canvas.reshape(G, C, C, 1)
         return self.generated_samples
 
-    # ------------------------------------------------------- outputs -------
+
+class Results:
+    """The result accessors of both models (mixed into ModelBase)."""
+
     def _T(self) -> int:
         live = self._ws.live.detach().cpu().numpy()
         return int(live[: self.max_steps].sum())

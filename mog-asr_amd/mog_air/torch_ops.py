@@ -368,7 +368,7 @@ def _svs_bwd(ctx, grads):
     dmb = torch.empty((B, 784), **bf)
     dth_b, dot = torch.empty((B, 6), **f32), torch.empty(B, **f32)
     ops.stn_backward(r, theta_b, (C, C), dpart.contiguous(), gscale=zc.contiguous(), want_dot=True,
-                     dtheta=dth_b, dot=dot, dm_bf16=dmb)
+                     dtheta=dth_b, dot=dot, dm=dmb)
     dd2b, dd1b = torch.empty((B, 512), **bf), torch.empty((B, 256), **bf)
     dz = torch.empty((B, 50), **f32)
     gemm_bf16([dmb], [wn[6]], [dd2b], B, 512, 784, 784, 784, 512, epi=BF_SOFTPLUS_BWD, aux=[d2b],

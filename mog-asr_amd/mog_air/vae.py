@@ -1,5 +1,5 @@
 """GlimpseVAE — the glimpse VAE's launch sequences (air/vae.py:5-48 behind
-the STN read, air_model.py:523-550), a mixin of AIRModel shared by the AIR and
+the STN read, air_model.py:523-550), a mixin of ModelBase shared by the AIR and
 AIR-ASR models.
 
 Every sequence is written once per precision and direction over the rows of
@@ -13,7 +13,7 @@ and ``_vae_decoder`` (generative layers), or one fused launch
 (``_fused_bf16_launch``, the fp32 one in ``_vae_forward_all``).  Backward:
 ``_vae_decoder_backward`` then ``_vae_encoder_backward``; the cotangent dm
 arrives through the output sigmoid from the STN write backward
-(AIRModel._stn_write_backward_all).
+(ModelBase._stn_write_backward_all).
 """
 from __future__ import annotations
 
@@ -35,6 +35,11 @@ def _rows(T, t0, t1):
     if (t0, t1) == (0, T):
         return lambda a: a
     return lambda a: a[t0:t1]
+
+
+def _step_rows(T, t):
+    """_rows of loop step t, or (t None) of all T steps."""
+    return _rows(T, 0, T) if t is None else _rows(T, t, t + 1)
 
 
 class GlimpseVAE:
@@ -65,65 +70,58 @@ class GlimpseVAE:
         launch): wn[name] = W [in][out8] (dX B operand) and either
         wf[name] = W^T in MFMA B-fragment order (fused step kernel) or
         wt[name] = W^T [out][in8] (unfused forward GEMMs)."""
-        if getattr(self, "_pack_version", None) == self.params.version:
-            return
-        if not hasattr(self, "_pack_args"):
-            bf = dict(device=self.device, dtype=torch.bfloat16)
-            self._wt, self._wn, self._wf = {}, {}, {}
-            srcs, dsts, dims = [], [], []
-            for n in self._VAE:
-                w = self._P("vae/" + n + "/weights")
-                I, O = w.shape
-                wn = self._wn[n] = torch.zeros((I, self._pad8(O)), **bf)
-                if self.fused_step:
-                    Np, Kp = (O + 15) // 16 * 16, (I + 31) // 32 * 32
-                    wf = self._wf[n] = torch.zeros((Np, Kp), **bf)
-                    fwd, fdims = wf, [I, O, O, Np, Kp, Kp, 2]
-                else:
-                    wt = self._wt[n] = torch.zeros((O, self._pad8(I)), **bf)
-                    fwd, fdims = wt, [I, O, O, O, wt.shape[1], wt.shape[1], 1]
-                srcs += [w, w]
-                dsts += [fwd, wn]
-                dims += fdims + [I, O, O, I, wn.shape[1], wn.shape[1], 0]
-            self._pack_args = (srcs, dsts, dims)
-        _ops.cvt_bf16_batch_(*self._pack_args)
-        self._pack_version = self.params.version
+        self._wcache.get("pack_bf16", self._pack_bf16_build)
+
+    def _pack_bf16_build(self):
+        bf = dict(device=self.device, dtype=torch.bfloat16)
+        self._wt, self._wn, self._wf = {}, {}, {}
+        srcs, dsts, dims = [], [], []
+        for n in self._VAE:
+            w = self._P("vae/" + n + "/weights")
+            I, O = w.shape
+            wn = self._wn[n] = torch.zeros((I, self._pad8(O)), **bf)
+            if self.fused_step:
+                Np, Kp = (O + 15) // 16 * 16, (I + 31) // 32 * 32
+                wf = self._wf[n] = torch.zeros((Np, Kp), **bf)
+                fwd, fdims = wf, [I, O, O, Np, Kp, Kp, 2]
+            else:
+                wt = self._wt[n] = torch.zeros((O, self._pad8(I)), **bf)
+                fwd, fdims = wt, [I, O, O, O, wt.shape[1], wt.shape[1], 1]
+            srcs += [w, w]
+            dsts += [fwd, wn]
+            dims += fdims + [I, O, O, I, wn.shape[1], wn.shape[1], 0]
+        return dsts, lambda: _ops.cvt_bf16_batch_(srcs, dsts, dims)
 
     def _pack_f32(self):
         """Refresh the fp32 MFMA B-fragment packs of the VAE weights (the fp32
         fused step's weight operand) after a parameter update: one launch."""
-        if getattr(self, "_pack32_version", None) == self.params.version:
-            return
-        if not hasattr(self, "_pack32_args"):
-            ws_, ks, ns, outs = [], [], [], []
-            for n in self._VAE:
-                w = self._P("vae/" + n + "/weights")
-                K, N = w.shape
-                ws_.append(w)
-                ks.append(int(K))
-                ns.append(int(N))
-                outs.append(torch.empty(((K + 15) // 16) * ((N + 15) // 16) * 256,
-                                        device=self.device))
-            self._wf32 = outs
-            self._pack32_args = (ws_, ks, ns, outs)
-        _ops.pack_frag_f32_(*self._pack32_args)
-        self._pack32_version = self.params.version
+        self._wcache.get("pack_f32", self._pack_f32_build)
+
+    def _pack_f32_build(self):
+        ws_, ks, ns, outs = [], [], [], []
+        for n in self._VAE:
+            w = self._P("vae/" + n + "/weights")
+            K, N = w.shape
+            ws_.append(w)
+            ks.append(int(K))
+            ns.append(int(N))
+            outs.append(torch.empty(((K + 15) // 16) * ((N + 15) // 16) * 256,
+                                    device=self.device))
+        self._wf32 = outs
+        return outs, lambda: _ops.pack_frag_f32_(ws_, ks, ns, outs)
 
     def _vae_wT(self):
         """W^T of rec_mean, rec_log_variance [Z][R2] and generative_1 [G1][Z],
-        transposed in one launch when the parameters changed (a captured step
-        records the launch: GraphCapture._capture resets the version)."""
+        transposed in one launch when the parameters changed."""
+        return self._wcache.get("vae_wT", self._vae_wT_build)
+
+    def _vae_wT_build(self):
         W2, R1, R2, Z, G1, G2 = self._vae_dims()
-        buf = self.__dict__.get("_vae_wT_buf")
-        if buf is None:
-            buf = self.__dict__["_vae_wT_buf"] = [
-                torch.empty((Z, R2), device=self.device), torch.empty((Z, R2), device=self.device),
-                torch.empty((G1, Z), device=self.device)]
-        if getattr(self, "_vae_wT_version", None) != self.params.version:
-            _ops.transpose32_batch_(buf, [self._P("vae/" + n + "/weights") for n in
-                                          ("rec_mean", "rec_log_variance", "generative_1")])
-            self._vae_wT_version = self.params.version
-        return buf
+        buf = [torch.empty((Z, R2), device=self.device), torch.empty((Z, R2), device=self.device),
+               torch.empty((G1, Z), device=self.device)]
+        return buf, lambda: _ops.transpose32_batch_(
+            buf, [self._P("vae/" + n + "/weights") for n in
+                  ("rec_mean", "rec_log_variance", "generative_1")])
 
     def _latent_nt(self, rows):
         """The fp32 latent layers as NT products of W^T copies (_vae_wT) below
@@ -143,19 +141,20 @@ class GlimpseVAE:
     def _w3(self):
         """The three bf16 pieces of the VAE weights the x3 input gradients read
         (W [in][out] -> [3][in][out]), refreshed when the parameters change."""
-        if getattr(self, "_w3_version", None) != self.params.version:
-            if getattr(self, "_w3_buf", None) is None:
-                self._w3_buf = {}
-                for n in self._X3_DX:
-                    I, O = self._P("vae/" + n + "/weights").shape
-                    self._w3_buf[n] = torch.empty((3, I, O), device=self.device,
-                                                  dtype=torch.bfloat16)
+        return self._wcache.get("w3", self._w3_build)
+
+    def _w3_build(self):
+        buf = {}
+        for n in self._X3_DX:
+            I, O = self._P("vae/" + n + "/weights").shape
+            buf[n] = torch.empty((3, I, O), device=self.device, dtype=torch.bfloat16)
+
+        def refresh():
             for n in self._X3_DX:
                 w = self._P("vae/" + n + "/weights")
                 I, O = w.shape
-                ops.split3_bf16(w, self._w3_buf[n], I, O, O, O, I * O)
-            self._w3_version = self.params.version
-        return self._w3_buf
+                ops.split3_bf16(w, buf[n], I, O, O, O, I * O)
+        return buf, refresh
 
     def _dx(self, dY, name, out, M, N, K, aux=None):
         """out[M,N] = dY W^T (W = vae/name/weights [N][K]) [* sigmoid(aux)]."""
@@ -269,7 +268,7 @@ class GlimpseVAE:
         # spread every layer over the chip, finish first -- same bits either way
         if self.precision == "fp32" and self.fused_f32 and TB >= self.FUSED_F32_MIN_ROWS:
             self._pack_f32()
-            gen = getattr(ws, "eps_x_offset", None) is not None
+            gen = ws.eps_x_offset is not None
             off = ws.eps_x_offset + t0 * B * (W2 // 4) if gen else 0
             bias = [self._P("vae/" + n + "/biases") for n in self._VAE]
             # (the pre-activations are not stored: None in their slots)
@@ -302,7 +301,7 @@ class GlimpseVAE:
         if self.windows_size != 28 or (R1, R2, Z, G1, G2) != (512, 256, 50, 256, 512):
             raise ValueError("the fused step kernel is compiled for the reference VAE shape")
         wt = [self._wf[k] for k in self._VAE]
-        gen = getattr(ws, "eps_x_offset", None) is not None
+        gen = ws.eps_x_offset is not None
         off = ws.eps_x_offset + t0 * ws.B * (W2 // 4) if gen else 0
         bias = [self._P("vae/" + k + "/biases") for k in self._VAE]
         _ops.stn_vae_step_(n, self.canvas_size, X, r_(ws.th_f), r_(ws.th_b), r_(ws.zmask),

@@ -1,14 +1,14 @@
-"""Weight gradients of the AIR train step (the TF MatMul / BiasAdd gradients
-of air/vae.py:18-46, the heads of air/air_model.py:458-520 and the LSTM
-kernel of :454-456): which GEMM form each runs on, how far it splits K, and
-on which stream (AIRModel mixes this in; it reads the model's workspace and
-parameters).
+"""Weight gradients both models run (the TF MatMul / BiasAdd gradients of
+air/vae.py:18-46 and the x rows of the LSTM kernel, air/air_model.py:454-456):
+which GEMM form each runs on, how far it splits K, and on which stream
+(ModelBase mixes this in; it reads the model's workspace and parameters).  The
+heads' and the recurrent rows' gradients are with each model's loop.
 
 Forms: the fp32 chain split-K GEMM (gemm_f32.hip, float atomics), the
 grouped one-launch form of a small batch (gemm_group.hip), fp32 operands on
 the bf16 matrix cores with exact three-piece splits (gemm_x3.hip: in-kernel
 or pre-split) and the bf16 configuration's bf16 GEMMs
-(gemm_bf16.hip).  Streams: from AIRModel.SIDE_MIN_BATCH the VAE's weight
+(gemm_bf16.hip).  Streams: from ModelBase.SIDE_MIN_BATCH the VAE's weight
 gradients run on the side stream, the heads' and the recurrent rows' on the
 third stream.
 """
@@ -18,6 +18,7 @@ import torch
 
 from . import ops
 from .ops import EPI_ATOMIC, gemm
+from .vae import _step_rows
 
 _ops = ops._ops
 
@@ -56,15 +57,20 @@ class WeightGradients:
     # 24,576 rows, scripts/wgrad_shapes.py)
     WGRAD_TN_X3_SPLITS = 16
 
+    def _vae_gw(self, layer):
+        return self._G("vae/" + layer + "/weights")
+
+    def _vae_gb(self, layer):
+        return self._G("vae/" + layer + "/biases")
+
     def _vae_weight_grads_bf16(self, ws, t=None):
         """The VAE weight gradients over all T*B rows (bf16 operands), or over
         loop step t's B rows (accumulated: the per-step form of AIR-ASR)."""
         TB = ws.B * self.max_steps if t is None else ws.B
-        v = (lambda x: x) if t is None else (lambda x: x[t])  # noqa: E731
+        v = _step_rows(self.max_steps, t)
         W2, R1, R2, Z, G1, G2 = self._vae_dims()
         Zp = self._pad8(Z)
-        g = lambda n: self._G("vae/" + n + "/weights")  # noqa: E731
-        gb = lambda n: self._G("vae/" + n + "/biases")  # noqa: E731
+        g, gb = self._vae_gw, self._vae_gb
         # (X, dY, layer, M, N, lda, ldb) of the seven layers
         probs = [(v(ws.gb), v(ws.da1b), "recognition_1", W2, R1, W2, R1),
                  (v(ws.a1b), v(ws.da2b), "recognition_2", R1, R2, R1, R2),
@@ -135,15 +141,10 @@ class WeightGradients:
     def _vae_wgrad_fp32(self, ws, name, t=None):
         """One VAE layer's weight / bias gradient over all T*B rows (fp32), or
         over loop step t's B rows (accumulated: the per-step form of AIR-ASR)."""
-        TB = ws.B * self.max_steps
+        TB = ws.B * self.max_steps if t is None else ws.B
+        v = _step_rows(self.max_steps, t)
         W2, R1, R2, Z, G1, G2 = self._vae_dims()
-        g = lambda n: self._G("vae/" + n + "/weights")  # noqa: E731
-        gb = lambda n: self._G("vae/" + n + "/biases")  # noqa: E731
-        if t is None:
-            v = lambda x: x  # noqa: E731
-        else:
-            TB = ws.B
-            v = lambda x: x[t]  # noqa: E731
+        g, gb = self._vae_gw, self._vae_gb
         if name == "recognition_1":
             self._dw_x3(v(ws.g), v(ws.da1), g(name), TB, W2, R1, W2, R1, gb(name))
         elif name == "recognition_2":
@@ -166,7 +167,7 @@ class WeightGradients:
         accuracy, K split over the XCDs, partials added in order --
         deterministic)."""
         TB = ws.B * self.max_steps if t is None else ws.B
-        v = (lambda x: x) if t is None else (lambda x: x[t])  # noqa: E731
+        v = _step_rows(self.max_steps, t)
         W2, R1, R2, Z, G1, G2 = self._vae_dims()
         probs = [(v(ws.g), v(ws.da1), "recognition_1", W2, R1),
                  (v(ws.a1), v(ws.da2), "recognition_2", R1, R2),
@@ -177,8 +178,7 @@ class WeightGradients:
                  (v(ws.d2), v(ws.dm), "gen_mean", G2, W2)]
         if (self.VAE_WGRAD_X3 and TB >= self.WGRAD_TN_MIN_ROWS
                 and all(M % 2 == 0 and N % 2 == 0 for _, _, _, M, N in probs)):
-            g = lambda n: self._G("vae/" + n + "/weights")  # noqa: E731
-            gb = lambda n: self._G("vae/" + n + "/biases")  # noqa: E731
+            g, gb = self._vae_gw, self._vae_gb
             flops = sum(2.0 * TB * M * N for _, _, _, M, N in probs)
             with self._timed("vae_wgrad_x3", ("mfma", flops, "fp32", "x3")):
                 ops.wgrad_tn_x3([p[0] for p in probs], [p[1] for p in probs],
@@ -190,86 +190,34 @@ class WeightGradients:
                      "generative_2", "gen_mean"):
             self._vae_wgrad_fp32(ws, name, t)
 
-    def _weight_grads_glimpse(self, ws):
-        """Weight gradients of the VAE and the five heads (every loop step at
-        once, K = T*B rows)."""
+    def _vae_weight_grads(self, ws, t=None):
+        """The VAE weight gradients of the model's precision (all T*B rows, or
+        loop step t's B rows, accumulated)."""
         if self.precision == "bf16":
-            self._vae_weight_grads_bf16(ws)
+            self._vae_weight_grads_bf16(ws, t)
         else:
-            self._vae_weight_grads_fp32(ws)
-        self._weight_grads_heads(ws)
+            self._vae_weight_grads_fp32(ws, t)
 
-    def _vae_weight_grads_async(self, ws):
+    def _vae_weight_grads_async(self, ws, first):
         """The VAE weight gradients on the side stream (ordered after
-        everything issued so far on the current stream); returns the events
-        that mark the heads' W1 refresh and their completion.  Below
-        SIDE_MIN_BATCH they run in line on the current stream (events None):
-        at the reference's batch of 64 the launches are a few microseconds
-        each, too short to hide a cross-stream wait."""
+        everything issued so far on the current stream), behind ``first()``
+        (a launch the main stream needs sooner: AIR's refresh of the heads'
+        W1); returns the events that mark ``first`` and their completion.
+        Below SIDE_MIN_BATCH they run in line on the current stream, without
+        ``first`` (events None): at the reference's batch of 64 the launches
+        are a few microseconds each, too short to hide a cross-stream wait."""
         if ws.B < self.SIDE_MIN_BATCH:
-            if self.precision == "bf16":
-                self._vae_weight_grads_bf16(ws)
-            else:
-                self._vae_weight_grads_fp32(ws)
+            self._vae_weight_grads(ws)
             return None, None
         side = self._fork(self._side_stream())
         with torch.cuda.stream(side):
-            # the heads' concatenated W1 (B operand of the dh GEMM) first:
-            # off the main stream, which waits for it only at that GEMM
-            self._w1cat()
-            w1_done = torch.cuda.Event()
-            w1_done.record(side)
-            if self.precision == "bf16":
-                self._vae_weight_grads_bf16(ws)
-            else:
-                self._vae_weight_grads_fp32(ws)
+            first()
+            first_done = torch.cuda.Event()
+            first_done.record(side)
+            self._vae_weight_grads(ws)
             done = torch.cuda.Event()
             done.record(side)
-        return w1_done, done
-
-    def _w1cat(self):
-        """[W1_0 .. W1_4] side by side ([H, 5 HS]): the B operand of the heads'
-        dh GEMM, refreshed when the parameters change."""
-        if getattr(self, "_w1cat_version", None) != self.params.version:
-            if getattr(self, "_w1cat_buf", None) is None:
-                H, HS = self.rnn_units, self.scale_hidden_units
-                self._w1cat_buf = torch.empty((H, 5 * HS), device=self.device)
-            torch.cat([self._P(h + "/hidden/weights") for h in self._HEADS], dim=1,
-                      out=self._w1cat_buf)
-            self._w1cat_version = self.params.version
-        return self._w1cat_buf
-
-    def _weight_grads_heads(self, ws):
-        H, HS, TB = self.rnn_units, self.scale_hidden_units, ws.B * self.max_steps
-        heads = list(enumerate(self._HEADS))
-        dhid = ws.dhid.view(TB, 5, HS)
-        g = self._G
-        if (self._wgroup is None and TB >= self.WGRAD_TN_MIN_ROWS
-                and H % 2 == 0 and HS % 2 == 0 and HS < 128):
-            # deterministic from the split-K batch sizes on: the five hidden
-            # layers on the grouped x3 kernel (splits added in order), the 1- /
-            # 2-column output layers by chunk partials added in chunk order
-            # (mog_heads_output_wgrad)
-            flops = 2.0 * TB * H * HS * 5
-            with self._timed("heads_wgrad_x3", ("mfma", flops, "fp32", "x3")):
-                ops.wgrad_tn_x3([ws.h] * 5, [dhid[:, zi] for zi, _ in heads],
-                                [g(h + "/hidden/weights") for _, h in heads],
-                                [g(h + "/hidden/biases") for _, h in heads],
-                                [(H, HS, H, 5 * HS, HS)] * 5, TB, self.WGRAD_TN_X3_SPLITS)
-            _ops.heads_output_wgrad_([ws.hid[zi] for zi, _ in heads],
-                                     [ws.dout[zi] for zi, _ in heads],
-                                     [g(h + "/output/weights") for _, h in heads],
-                                     [g(h + "/output/biases") for _, h in heads],
-                                     [2 if h.startswith("shift") else 1 for _, h in heads], TB, HS)
-            return
-        self._dw([ws.h] * 5, [dhid[:, zi] for zi, _ in heads],
-                 [g(h + "/hidden/weights") for _, h in heads], TB, H, HS, H, 5 * HS,
-                 [g(h + "/hidden/biases") for _, h in heads])
-        for k in (1, 2):
-            sel = [(zi, h) for zi, h in heads if (2 if h.startswith("shift") else 1) == k]
-            self._dw([ws.hid[zi] for zi, _ in sel], [ws.dout[zi] for zi, _ in sel],
-                     [g(h + "/output/weights") for _, h in sel], TB, HS, k, HS, 2,
-                     [g(h + "/output/biases") for _, h in sel])
+        return first_done, done
 
     # fp32 configuration: the x-part of the LSTM kernel gradient on the bf16
     # matrix cores with exact three-piece operand splits (gemm_x3.hip,
@@ -278,108 +226,55 @@ class WeightGradients:
     # 244 vs 428 us stand-alone, step 3.44 -> 3.37 ms); 1: split inside the
     # GEMM (318 us, no change in the step); 0: the fp32 MFMA split-K GEMM.
     X_GRAD_X3 = 2
-    # the pre-split form from this batch: below it (the reference's batch of
-    # 64) the two split launches cost more than the fp32 chain's K = B pass
+    # the pre-split form from this batch in the AIR model (_x3p_xgrad; the
+    # AIR-ASR model's gate is _x3_asr): below it (the reference's batch of 64)
+    # the two split launches cost more than the fp32 chain's K = B pass
     # (batch 64: x3p 12.3 + splits 9.6 us)
     X3P_MIN_B = 256
-
-    def _x3p_xgrad(self, B):
-        return self.precision == "fp32" and self.X_GRAD_X3 == 2 and B >= self.X3P_MIN_B
     X3_SPLITK = 8
 
-    # rows of the x-part of the LSTM kernel gradient per all-reduce bucket
+    # rows of the x-part of the AIR LSTM kernel gradient per all-reduce bucket
     # (multiple of the 64-row GEMM tile; data parallel only)
     X_GRAD_CHUNK = 640
 
-    def _weight_grads_rec_side(self, ws):
-        """One GPU: the LSTM kernel's recurrent-rows gradient sum_t h[t-1]^T
-        dG[t] on a side stream, forked as soon as dG[1:] is final (before the
-        chain's step 0), so it overlaps that step instead of the x-rows
-        gradient."""
-        # (on the third stream after the heads' weight gradients: 3.06 ->
-        # 3.04 ms against the side stream)
-        with torch.cuda.stream(self._fork(self._stream3())):
-            self._dw_rec(ws)
-
-    def _dw_rec(self, ws):
-        """The LSTM kernel's recurrent rows: gK[C2:] += sum_t h[t-1]^T dG[t]
-        over (T-1) B rows.  From WGRAD_TN_MIN_ROWS (either precision:
-        fp32-level, and faster than the fp32 chain): on the bf16 matrix cores
-        with exact three-piece splits (the grouped x3 kernel of the fp32 VAE
-        weight gradients, one problem, 256 x 1024 x 16,384 at B = 8192), else
-        the fp32 split-K GEMM."""
-        B, T, H, C2 = ws.B, self.max_steps, self.rnn_units, self.C2
-        gK = self._G("rnn/basic_lstm_cell/kernel")
-        K = (T - 1) * B
-        if self.REC_WGRAD_X3 and K >= self.WGRAD_TN_MIN_ROWS:
-            # the grouped x3 kernel with one problem: deterministic
-            with self._timed("rec_wgrad_x3", ("mfma", 2.0 * K * H * 4 * H, "fp32", "x3")):
-                ops.wgrad_tn_x3([ws.h], [ws.dG[1:]], [gK[C2:]], [None],
-                                [(H, 4 * H, H, 4 * H, 4 * H)], K, self.WGRAD_TN_X3_SPLITS)
-        else:
-            self._dw(ws.h, ws.dG[1:], gK[C2:], K, H, 4 * H, H, 4 * H)
-
+    # the LSTM kernels' recurrent-rows gradients on the grouped x3 kernel
+    # (AIRModel._dw_rec, the AIR-ASR model's _u_rows_wgrad)
     REC_WGRAD_X3 = True
 
-    def _weight_grads_lstm(self, X, ws, side=False, rec_done=False):
-        """LSTM kernel / bias gradients.  Data parallel: the x-part X^T dGsum
-        (2500 x 1024, 10 MB) is produced in row chunks, each handed to the
-        all-reduce as soon as it is final, so the collective of chunk i runs
-        under the GEMM of chunk i+1; the recurrent rows and the bias go last.
-        rec_done: the recurrent rows were forked already (_weight_grads_rec_side)."""
-        B, T, H, C2 = ws.B, self.max_steps, self.rnn_units, self.C2
-        gK = self._G("rnn/basic_lstm_cell/kernel")
-        gbK = self._G("rnn/basic_lstm_cell/bias")
-        if rec_done:
-            pass
-        elif T > 1 and side and self.REC_WGRAD_SIDE:
-            self._weight_grads_rec_side(ws)
-        elif T > 1:
-            self._dw_rec(ws)
-        chunk = self.X_GRAD_CHUNK if self.grad_reducer is not None else C2
-        base = self.params.offsets[self._SCOPE_PREFIX + "rnn/basic_lstm_cell/kernel"]
-        # bias gradient = colsum(sum_t dG_t) = colsum(dGsum), fused into chunk 0
-        m_last = 0
-        # (the x-rows gradient GEMM of every chunk is tagged; its operand
-        # conversions / splits are not: they are other launches)
-        x3p = self._x3p_xgrad(B)
-        for m0 in range(0, C2, chunk):
-            m_last = m0
-            m1 = min(C2, m0 + chunk)
-            bias = gbK if m0 == 0 else None
-            if self.precision == "bf16":
-                # bf16 configuration: X^T dGsum on bf16 operands (fp32
-                # accumulate); the forward x-projection stays fp32
-                self._x_grad_bf16(X, ws, gK, bias, m0, m1)
-            elif x3p:
-                if m0 == 0:
-                    if getattr(ws, "dG3", None) is None:
-                        ws.dG3 = torch.empty((3, B, 4 * H), device=self.device,
-                                             dtype=torch.bfloat16)
-                    # the pieces of sum_t dG_t, summed in the reversed loop's
-                    # order without the running sum (mog_split3_sum_bf16)
-                    _ops.split3_sum_bf16_(ws.dG, T, B * 4 * H, ws.dG3, B, 4 * H, 4 * H, 4 * H,
-                                          B * 4 * H)
+    def _x_split3(self, X, ws):
+        """X in three exact bf16 pieces [3][B][C2p] (ws.X3): the A operand of
+        the pre-split x-rows gradient, split once per step in the forward's
+        prologue (X is the step's input, final before the x-projection)."""
+        B, C2 = ws.B, self.C2
+        C2p = self._pad8(C2)
+        ops.split3_bf16(X, ws.buffer("X3", (3, B, C2p), torch.bfloat16), B, C2, C2, C2p, B * C2p)
+
+    def _x_rows_grad(self, X, ws, gK, bias_out, m0, m1, x3p):
+        """Rows [m0, m1) of the LSTM kernel's x-rows gradient gK[:C2] += X^T
+        sum_t dG_t (the x input is loop-invariant), bias_out += its column
+        sums.  bf16: bf16 operands (fp32 accumulate; the forward x-projection
+        stays fp32).  fp32: on the bf16 matrix cores from exact three-piece
+        splits of both operands (gemm_x3.hip, DESIGN.md §4.4: fp32-level
+        accuracy) -- x3p: the pieces the model prepared in ws.X3 / ws.dG3;
+        X_GRAD_X3 = 1: split inside the GEMM -- or the fp32 split-K chain.
+        (The GEMM of every chunk is tagged; the operand conversions / splits
+        are other launches.)"""
+        B, H, C2 = ws.B, self.rnn_units, self.C2
+        if self.precision == "bf16":
+            return self._x_grad_bf16(X, ws, gK, bias_out, m0, m1)
+        if not x3p and self.X_GRAD_X3 != 1:
+            return self._dw(X[:, m0:], ws.dGsum, gK[m0:m1], B, m1 - m0, 4 * H, C2, 4 * H, bias_out)
+        splitk = self._sk(max(1, min(B // 256, self.X3_SPLITK)))
+        with self._timed("lstm_x_projection_grad",
+                         ("mfma", 2.0 * B * (m1 - m0) * 4 * H, "fp32", "x3")):
+            if x3p:
                 C2p = self._pad8(C2)
-                with self._timed("lstm_x_projection_grad",
-                                 ("mfma", 2.0 * B * (m1 - m0) * 4 * H, "fp32", "x3")):
-                    ops.gemm_x3p_tn(ws.X3.view(-1)[m0:], B * C2p, ws.dG3, B * 4 * H, gK[m0:m1],
-                                    m1 - m0, 4 * H, B, C2p, 4 * H, 4 * H,
-                                    splitk=self._sk(max(1, min(B // 256, self.X3_SPLITK))),
-                                    colsum=bias, reduce=True)
-            elif self.X_GRAD_X3 == 1:
-                # fp32 operands split exactly into three bf16 pieces on the
-                # bf16 matrix cores (gemm_x3.hip: fp32-level accuracy)
-                with self._timed("lstm_x_projection_grad",
-                                 ("mfma", 2.0 * B * (m1 - m0) * 4 * H, "fp32", "x3")):
-                    ops.gemm_x3_tn(X[:, m0:], ws.dGsum, gK[m0:m1], m1 - m0, 4 * H, B, C2, 4 * H,
-                                   4 * H, splitk=self._sk(max(1, min(B // 256, self.X3_SPLITK))),
-                                   colsum=bias)
+                ops.gemm_x3p_tn(ws.X3.view(-1)[m0:], B * C2p, ws.dG3, B * 4 * H, gK[m0:m1],
+                                m1 - m0, 4 * H, B, C2p, 4 * H, 4 * H, splitk=splitk,
+                                colsum=bias_out, reduce=True)
             else:
-                self._dw(X[:, m0:], ws.dGsum, gK[m0:m1], B, m1 - m0, 4 * H, C2, 4 * H, bias)
-            if m1 < C2:
-                self._reduce_bucket(base + m0 * 4 * H, base + m1 * 4 * H)
-        self._reduce_bucket(base + m_last * 4 * H, self._bucket_split())
+                ops.gemm_x3_tn(X[:, m0:], ws.dGsum, gK[m0:m1], m1 - m0, 4 * H, B, C2, 4 * H,
+                               4 * H, splitk=splitk, colsum=bias_out)
 
     def _x_bf16(self, X, ws):
         """X in bf16 [B][C2p] (zero pad columns): the A operand of the bf16
@@ -388,9 +283,8 @@ class WeightGradients:
         input, final before the x-projection)."""
         B, C2 = ws.B, self.C2
         C2p = self._pad8(C2)
-        if getattr(ws, "Xb", None) is None:
-            ws.Xb = torch.zeros((B, C2p), device=self.device, dtype=torch.bfloat16)
-        _ops.cvt_bf16_batch_([X], [ws.Xb], [B, C2, C2, B, C2p, C2p, 0])
+        Xb = ws.buffer("Xb", (B, C2p), torch.bfloat16)
+        _ops.cvt_bf16_batch_([X], [Xb], [B, C2, C2, B, C2p, C2p, 0])
         ws.xb_fresh = True
 
     def _x_grad_bf16(self, X, ws, gK, bias_out, m0, m1):
@@ -400,15 +294,14 @@ class WeightGradients:
         B, H, C2 = ws.B, self.rnn_units, self.C2
         C2p = self._pad8(C2)
         if m0 == 0:
-            if not getattr(ws, "xb_fresh", False):  # (no conversion in this step's forward)
+            if not ws.xb_fresh:  # (no conversion in this step's forward)
                 self._x_bf16(X, ws)
             ws.xb_fresh = False
-            if getattr(ws, "xb_ready", None) is not None:  # (converted on the side stream)
+            if ws.xb_ready is not None:  # (converted on the side stream)
                 torch.cuda.current_stream().wait_event(ws.xb_ready)
                 ws.xb_ready = None
-            if getattr(ws, "dGsumb", None) is None:
-                ws.dGsumb = torch.empty((B, 4 * H), device=self.device, dtype=torch.bfloat16)
-            _ops.cvt_bf16_batch_([ws.dGsum], [ws.dGsumb], [B, 4 * H, 4 * H, B, 4 * H, 4 * H, 0])
+            dGsumb = ws.buffer("dGsumb", (B, 4 * H), torch.bfloat16)
+            _ops.cvt_bf16_batch_([ws.dGsum], [dGsumb], [B, 4 * H, 4 * H, B, 4 * H, 4 * H, 0])
         # split-K 8 at B = 8192, partials summed through the workspace
         # (scripts/x1_sweep.py, us for 1/2/3/4/6/8 splits: 138/84/77/73/73/72;
         # with float atomics 77/76/81/88 from 3 splits)

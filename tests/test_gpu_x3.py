@@ -139,6 +139,30 @@ def test_x3_fp32_step_gradients_match_chain():
             assert (a - b).abs().max().item() <= 1e-5 * (b.abs().max().item() + 1e-30), k
 
 
+def test_x_rows_gradient_past_eight_steps_takes_the_chain():
+    """mog_split3_sum_bf16 sums at most 8 steps' dG, so an fp32 AIR model
+    with max_steps = 9 leaves the pre-split x-rows gradient even at
+    X3P_MIN_B (256, the smallest batch that would take it): the backward
+    accumulates dGsum and runs the fp32 chain, the launches of X_GRAD_X3 = 0
+    -- every gradient bit for bit (one k pass per weight gradient)."""
+    from mog_air.air_model import AIRModel
+    rng = np.random.default_rng(9)
+    B = AIRModel.X3P_MIN_B
+    assert B == 256
+    x = (rng.uniform(size=(B, 2500)) * (rng.uniform(size=(B, 2500)) < 0.3)).astype(np.float32)
+    grads = []
+    for x3 in (AIRModel.X_GRAD_X3, 0):
+        m = AIRModel(max_steps=9, canvas_size=50, cnn=False, train=True, scope="x3t9_%d" % x3,
+                     device=DEV, precision="fp32", seed=3, noise_seed=4)
+        m.X_GRAD_X3 = x3
+        m.ONE_PASS_WGRADS = True
+        assert not m._x3p_xgrad(B)
+        grads.append(m.compute_gradients(x))
+    assert grads[0].keys() == grads[1].keys()
+    for k in grads[0]:
+        np.testing.assert_array_equal(grads[0][k], grads[1][k], err_msg=k)
+
+
 @pytest.mark.parametrize("M,N,K,m0,splitk", [(2500, 1024, 4096, 0, 8), (580, 1024, 777, 1920, 1),
                                              (132, 40, 300, 0, 2)])
 def test_x1_plain_bf16_operands(M, N, K, m0, splitk):

@@ -153,6 +153,53 @@ def test_param_store_layout_cpu():
     assert st.n_blocks == sum(-(-int(np.prod(s)) // 4096) for _, s in specs)
 
 
+def test_weight_cache_builds_once_and_refreshes_per_version():
+    """params.WeightCache: buffers derived from the weights are built on first
+    use, refreshed once per params.version change, and again after
+    invalidate() (a graph capture records the refresh without running it)."""
+    from types import SimpleNamespace
+
+    from mog_air.params import WeightCache
+    params = SimpleNamespace(version=3)
+    cache = WeightCache(params)
+    calls = {"build": 0, "refresh": 0, "other": 0}
+    buf = object()
+
+    def build():
+        calls["build"] += 1
+        return buf, lambda: calls.__setitem__("refresh", calls["refresh"] + 1)
+
+    assert calls == {"build": 0, "refresh": 0, "other": 0}  # nothing before the first use
+    assert cache.get("w", build) is buf
+    assert cache.get("w", build) is buf
+    assert (calls["build"], calls["refresh"]) == (1, 1)
+    params.version += 1
+    assert cache.get("w", build) is buf
+    assert cache.get("w", build) is buf
+    assert (calls["build"], calls["refresh"]) == (1, 2)
+    # a second name has its own version; invalidate() forgets both
+    other = cache.get("o", lambda: ("o", lambda: calls.__setitem__("other", calls["other"] + 1)))
+    assert other == "o" and calls["other"] == 1
+    cache.invalidate()
+    assert cache.get("w", build) is buf and cache.get("o", build) == "o"
+    assert (calls["build"], calls["refresh"], calls["other"]) == (1, 3, 2)
+    assert cache.get("w", build) is buf
+    assert (calls["build"], calls["refresh"]) == (1, 3)
+
+
+def test_workspace_reads_of_undeclared_fields_raise():
+    """model_base._Workspace.buffer allocates only declared buffers: a
+    misspelt name is an AttributeError, not 'not allocated yet'."""
+    from mog_air.model_base import _Workspace
+    ws = _Workspace.__new__(_Workspace)
+    ws.device, ws.Xb, ws.dG3 = torch.device("cpu"), None, None
+    assert ws.buffer("dG3", (3, 2, 4), torch.bfloat16).shape == (3, 2, 4)
+    assert ws.buffer("dG3", (3, 2, 4), torch.bfloat16) is ws.dG3
+    assert "Xb" in ws.ZERO_PADDED and not ws.buffer("Xb", (2, 8), torch.bfloat16).any()
+    with pytest.raises(AttributeError):
+        ws.buffer("dG_3", (3, 2, 4))
+
+
 def test_annealing_matches_oracle():
     from mog_air.air_model import annealed_value
     sched = {"init": 10000.0, "min": 1e-9, "factor": 0.1, "iters": 3000,
