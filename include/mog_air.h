@@ -546,6 +546,32 @@ int mog_asr_step_backward(int B, int train, int fix_steps, float temperature,
                           const float* dtheta_back, const float* dot, const float* dreg,
                           const float* dss, float* douts, float* const* dpre, void* stream);
 
+/* ---- AIR-ASR generation (air_number_bbox_location.py:1124-1361) ----------
+ * One step of the generation loop for G images, after the generative
+ * LSTMCell and the hidden layers: hid[3] [G,64] = relu hidden rows of
+ * gen_shift dense / dense_2 on the new output hg and of z_pres/prior dense on
+ * the previous output (null with fix_steps >= 0); w[6] = gen_shift dense_1
+ * W,b, dense_3 W,b [64,2], z_pres/prior dense_1 W,b [64,1] (the last two may
+ * be null with fix_steps >= 0).  shift latent = m + eps_shift sqrt(exp(lv)),
+ * scale latent = scale_prior_mean + eps_scale sqrt(scale_prior_var) (ss
+ * [G,3]), z = vae_prior_mean + eps_z sqrt(exp(vae_prior_logvar)); theta_back
+ * = [[1/s, 0, -tanh(x)/s], [0, 1/s, -tanh(y)/s]] with the constant s > 0
+ * (:1203-1205); prior log-odds +-100 by step < fix_steps, or the learned
+ * chain; zval = rint(sigmoid((lo + logistic(u)) / temperature)); stop += 1 -
+ * zval; zmask = stop < thr; digits += zmask; live[step + 1] = 1 if any image
+ * is still counting (live [T+1], as mog_asr_step_forward). */
+int mog_asr_gen_step(int G, int Z, int step, int fix_steps, float thr, float temperature,
+                     float scale_prior_mean, float scale_prior_var, float s,
+                     float vae_prior_mean, float vae_prior_logvar, const float* const* w,
+                     const float* const* hid, const float* eps_shift, const float* eps_scale,
+                     const float* eps_z, const float* u, float* stop, int* digits, int* live,
+                     float* ss, float* z, float* theta_back, float* zval, float* zmask,
+                     void* stream);
+/* out[i] = x[i] > u[i] ? 1 : 0 for n floats: the Bernoulli sample of the
+ * decoded window (vae.py:83-84 relu(sign(samples - U))).  16-byte vector
+ * accesses when x, u and out are 16-byte aligned; out may be x or u. */
+int mog_bernoulli_threshold(const float* x, const float* u, float* out, long n, void* stream);
+
 /* ---- noise (tf.random_normal / random_uniform sites, perf mode) --------- */
 int mog_rng_fill(float* out, long n, unsigned long long seed, unsigned long long offset,
                  int normal, void* stream);

@@ -981,6 +981,52 @@ void asr_step_forward_(int64_t B, int64_t step, bool train, int64_t fix_steps, d
         o.name);
 }
 
+// one step of the generation loop (asr_gen.hip; :1124-1361)
+void asr_gen_step_(int64_t G, int64_t Z, int64_t step, int64_t fix_steps, double thr,
+                   double temperature, double s_pm, double s_pv, double s, double v_pm,
+                   double v_plv, const c10::List<optional<Tensor>>& w,
+                   const c10::List<optional<Tensor>>& hid, const Tensor& eps_shift,
+                   const Tensor& eps_scale, const Tensor& eps_z, const Tensor& u, Tensor stop,
+                   Tensor digits, Tensor live, Tensor ss, Tensor z, Tensor theta_back, Tensor zval,
+                   Tensor zmask) {
+  Op o("asr_gen_step_");
+  TORCH_CHECK(w.size() == 6 && hid.size() == 3, o.name, ": 3 output layers, 3 hidden layers");
+  TORCH_CHECK(step >= 0, o.name, ": step");
+  float* pst = o.f(stop, G, "stop");
+  // gen_shift dense_1 / dense_3 [64,2] + [2], z_pres/prior dense_1 [64,1] + [1]
+  const int64_t wext[6] = {128, 2, 128, 2, 64, 1};
+  vector<void*> pw;
+  for (size_t k = 0; k < 6; ++k)
+    pw.push_back(o.f(static_cast<optional<Tensor>>(w[k]), wext[k], "w"));
+  auto ph = o.list(hid, F32, G * 64, "hid");
+  float* peh = o.f(eps_shift, 2 * G, "eps_shift");
+  float* pes = o.f(eps_scale, G, "eps_scale");
+  float* pez = o.f(eps_z, G * Z, "eps_z");
+  float* pu = o.f(u, G, "u");
+  int* pd = o.i(digits, G, "digits");
+  int* pl = o.i(live, step + 2, "live");
+  float* pss = o.f(ss, 3 * G, "ss");
+  float* pz = o.f(z, G * Z, "z");
+  float* ptb = o.f(theta_back, 6 * G, "theta_back");
+  float* pzv = o.f(zval, G, "zval");
+  float* pzm = o.f(zmask, G, "zmask");
+  GUARD(o);
+  check(mog_asr_gen_step(G, Z, step, fix_steps, thr, temperature, s_pm, s_pv, s, v_pm, v_plv,
+                         arr<float>(pw), arr<float>(ph), peh, pes, pez, pu, pst, pd, pl, pss, pz,
+                         ptb, pzv, pzm, o.stream()),
+        o.name);
+}
+
+void bernoulli_threshold_(const Tensor& x, const Tensor& u, Tensor out, int64_t n) {
+  Op o("bernoulli_threshold_");
+  float* po = o.f(out, n, "out");
+  float* px = o.f(x, n, "x");
+  float* pu = o.f(u, n, "u");
+  TORCH_CHECK(n >= 0, o.name, ": n");
+  GUARD(o);
+  check(mog_bernoulli_threshold(px, pu, po, n, o.stream()), o.name);
+}
+
 void asr_terms_(int64_t B, int64_t T, int64_t C, at::IntArrayRef cons, at::ArrayRef<double> gammas,
                 const Tensor& rec, const Tensor& vkl, const Tensor& zmask, const Tensor& live,
                 Tensor klsum, Tensor pr, Tensor area, Tensor out, Tensor size, Tensor overlap,
@@ -1442,6 +1488,13 @@ TORCH_LIBRARY_FRAGMENT(mog_air, m) {
       "Tensor(g!) theta_back, Tensor(h!) ss, Tensor(i!) scale, Tensor(j!) shift, "
       "Tensor(k!) zprob, Tensor(l!) zmask, Tensor(m!) zval, Tensor(n!) zc) -> ()");
   m.def(
+      "asr_gen_step_(int G, int Z, int step, int fix_steps, float thr, float temperature, "
+      "float s_pm, float s_pv, float s, float v_pm, float v_plv, Tensor?[] w, Tensor?[] hid, "
+      "Tensor eps_shift, Tensor eps_scale, Tensor eps_z, Tensor u, Tensor(a!) stop, "
+      "Tensor(b!) digits, Tensor(c!) live, Tensor(d!) ss, Tensor(e!) z, Tensor(f!) theta_back, "
+      "Tensor(g!) zval, Tensor(h!) zmask) -> ()");
+  m.def("bernoulli_threshold_(Tensor x, Tensor u, Tensor(a!) out, int n) -> ()");
+  m.def(
       "asr_terms_(int B, int T, int C, int[] cons, float[] gammas, Tensor rec, Tensor vkl, "
       "Tensor zmask, Tensor live, Tensor(a!) klsum, Tensor(b!) pr, Tensor(c!) area, "
       "Tensor(d!) out, Tensor(e!) size, Tensor(f!) overlap, Tensor(g!) zsum) -> ()");
@@ -1509,6 +1562,8 @@ TORCH_LIBRARY_IMPL(mog_air, CUDA, m) {
   m.impl("asr_pack_", &asr_pack_);
   m.impl("asr_unpack_", &asr_unpack_);
   m.impl("asr_step_forward_", &asr_step_forward_);
+  m.impl("asr_gen_step_", &asr_gen_step_);
+  m.impl("bernoulli_threshold_", &bernoulli_threshold_);
   m.impl("asr_terms_", &asr_terms_);
   m.impl("asr_finalize_", &asr_finalize_);
   m.impl("asr_terms_backward_", &asr_terms_backward_);

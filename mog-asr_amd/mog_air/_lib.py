@@ -93,6 +93,9 @@ _SIGS = {
     "mog_asr_finalize": [I, I, I, I, P, P, F, P, P, P, P, P, P, P, P],
     "mog_asr_terms_backward": [I, I, I, I, P, P, F, F, P, P, P, P, P],
     "mog_asr_step_backward": [I, I, I, F, F, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P],
+    "mog_asr_gen_step": [I, I, I, I, F, F, F, F, F, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P,
+                         P, P],
+    "mog_bernoulli_threshold": [P, P, P, L, P],
 }
 
 # entry points that do not return an int status

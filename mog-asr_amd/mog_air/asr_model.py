@@ -18,6 +18,9 @@ Loop: max_steps iterations on the device, the data-dependent predicate
 (:386-390) folded into a live flag per step; losses, counts and gradients
 equal the early exit.  The KL records are summed per type over the executed
 steps at the end, as the reference's TensorArrays are (:917-923).
+
+Generation (:1124-1361): ``generate()`` runs the generative LSTMCell as the
+prior over positions and counts (asr_gen.hip), the same fixed-T schedule.
 """
 from __future__ import annotations
 
@@ -27,7 +30,7 @@ import torch
 
 from . import ops
 from .model_base import ModelBase, _Workspace
-from .ops import EPI_RELU, EPI_STORE, gemm
+from .ops import EPI_RELU, EPI_SIGMOID_NOISE, EPI_SOFTPLUS, EPI_STORE, gemm
 from .vae import _step_rows
 
 _ops = ops._ops  # torch.ops.mog_air (csrc/torch_ops.cpp)
@@ -640,6 +643,108 @@ class AIRModel(ModelBase):
                 "num_margin": float(ws.margin[0]), "num_min_KL": m(ws.element),
                 "TotLoss": self.loss, "elbo": m(ws.klsum + ws.bce), "accu": self.accuracy}
 
-    def generate(self, *a, **k):
-        raise NotImplementedError("ASR generation (air_number_bbox_location.py:1124-1361) runs "
-                                  "the generative LSTM prior; not part of this build")
+    # ------------------------------------------------------ generation -----
+    _GEN_NOISE = (("eps_shift", True), ("eps_scale", True), ("eps_z", True), ("eps_x", True),
+                  ("u_x", False), ("u", False))
+
+    def generate(self, batch=None, noise=None):
+        """The test model's ``generated_samples``
+        (air_number_bbox_location.py:1124-1361, vae.py:51-86): up to
+        ``max_steps`` objects per canvas.  Each step runs the generative
+        LSTMCell on [z_prev, latents_prev], draws the shift latent from the
+        gen_shift heads, the scale latent from the fixed scale prior and z
+        from the VAE prior, decodes and binarises the window
+        (``sample_from_mean``), and writes it where the rounded z_pres sample
+        (fixed +-100 prior with ``fix_steps``, else the learned prior on the
+        previous generative output) keeps the image counting.  The write
+        scale is the constant mean(constrains_area_minmax) / canvas_size
+        (:1203-1205); where that mean is not positive the reference builds
+        infinite transforms, and this raises ``ValueError`` instead.
+
+        Returns the canvas [G, C, C, 1]; ``generated_st_back`` [G, T_exec, 2,
+        3] and ``generated_num_digits`` [G] hold the loop's other outputs.
+        ``noise`` (optional) injects eps_shift [T,G,2], eps_scale [T,G], eps_z
+        [T,G,Z], eps_x [T,G,W2], u_x [T,G,W2], u [T,G] (T = max_steps);
+        otherwise device Philox noise is drawn in that order.  The loop runs
+        max_steps iterations on the device without a host synchronisation
+        (steps past the reference's exit write nothing); the executed count is
+        read back once at the end.  Runs the fp32 GEMMs in either precision."""
+        G = int(batch if batch is not None else self.generation_batch_size)
+        T, C, W2, Z, H = self.max_steps, self.canvas_size, self.W2, self.vae_latent_dimensions, \
+            self.rnn_units
+        area = sum(self.constrains_area_minmax) / len(self.constrains_area_minmax)
+        if not area > 0:
+            raise ValueError("generation writes at the scale mean(constrains_area_minmax) / "
+                             f"canvas_size, which must be positive (got {area / C})")
+        s = torch.tensor(area / C, dtype=torch.float32).item()  # one cast of the double quotient
+        G1, G2 = self.vae_generative_units
+        dev = self.device
+        e = lambda *sh: torch.empty(sh, device=dev, dtype=torch.float32)  # noqa: E731
+        eps = {"eps_shift": e(T, G, 2), "eps_scale": e(T, G), "eps_z": e(T, G, Z),
+               "eps_x": e(T, G, W2), "u_x": e(T, G, W2), "u": e(T, G)}
+        for k, normal in self._GEN_NOISE:
+            buf = eps[k]
+            if noise is not None:
+                src = torch.as_tensor(noise[k], dtype=torch.float32)
+                if tuple(src.shape) != tuple(buf.shape):
+                    raise ValueError(f"noise[{k}] has shape {tuple(src.shape)}, expected "
+                                     f"{tuple(buf.shape)}")
+                buf.copy_(src)
+            else:
+                ops.rng_fill(buf, self.noise_seed, self._noise_ctr, normal)
+                self._noise_ctr += (buf.numel() + 3) // 4
+        canvas, stop = e(G, C * C), e(G)
+        digits = torch.empty(G, device=dev, dtype=torch.int32)
+        live = torch.empty(T + 1, device=dev, dtype=torch.int32)
+        hg_zero = e(G, H)
+        _ops.fill32_batch_([canvas, stop, digits, live[:1], live[1:], hg_zero], [0, 0, 0, 1, 0, 0])
+        Ug, Gg, cg, hg = e(G, LU), e(G, 4 * H), e(2, G, H), e(2, G, H)
+        hid = e(3, G, 64)
+        ss, z, st_back = e(2, G, 3), e(2, G, Z), e(T, G, 6)
+        zval, zmask = e(G), e(G)
+        d1, d2, r, win = e(G, G1), e(G, G2), e(G, W2), e(G, W2)
+        Kg, bg = self._Kpad("gen_rnn_running/kernel"), self._P("gen_rnn_running/bias")
+        fix = self._fix
+        heads = ["gen_shift/dense", "gen_shift/dense_2"] + (["z_pres/prior/dense"] if fix < 0 else [])
+        relu_w = [self._P(n + "/kernel") for n in heads]
+        relu_b = [self._P(n + "/bias") for n in heads]
+        outs = ("gen_shift/dense_1", "gen_shift/dense_3", "z_pres/prior/dense_1")
+        w6 = [self._P(n + p) for n in outs for p in ("/kernel", "/bias")]
+        vw = {n: self._P("vae/" + n + "/weights") for n in ("generative_1", "generative_2",
+                                                            "gen_mean")}
+        vb = {n: self._P("vae/" + n + "/biases") for n in vw}
+        thr, temp = self.hyper("stopping_threshold"), self.hyper("z_pres_temperature")
+        lik_std = float(self.hyper("vae_likelihood_std"))
+        for t in range(T):
+            cur, prv = t % 2, (t - 1) % 2
+            prev = t > 0
+            _ops.asr_pack_(G, Z, H, LU, z[prv] if prev else None, ss[prv] if prev else None,
+                           hg[prv] if prev else None, Ug, None, None)
+            # K = LU: the packed rows and the kernel's pad rows end in zeros (_forward)
+            gemm([Ug], [Kg], [Gg], G, 4 * H, LU, LU, 4 * H, 4 * H, bias=[bg])
+            _ops.lstm_cell_forward_(Gg, None, cg[prv] if prev else None, cg[cur], hg[cur], G, H)
+            # the gen_shift hidden layers on the new output and the learned
+            # prior's on the previous one (:1259-1272), one batched launch
+            ra = [hg[cur]] * 2 + ([hg[prv] if prev else hg_zero] if fix < 0 else [])
+            gemm(ra, relu_w, [hid[k] for k in range(len(ra))], G, 64, H, H, 64, 64, epi=EPI_RELU,
+                 bias=relu_b)
+            _ops.asr_gen_step_(G, Z, t, fix, thr, temp, float(self.scale_prior_mean),
+                               float(self.scale_prior_variance), s, float(self.vae_prior_mean),
+                               self.vae_prior_log_variance, w6,
+                               [hid[0], hid[1], hid[2] if fix < 0 else None], eps["eps_shift"][t],
+                               eps["eps_scale"][t], eps["eps_z"][t], eps["u"][t], stop, digits,
+                               live, ss[cur], z[cur], st_back[t], zval, zmask)
+            gemm([z[cur]], [vw["generative_1"]], [d1], G, G1, Z, Z, G1, G1, epi=EPI_SOFTPLUS,
+                 bias=[vb["generative_1"]])
+            gemm([d1], [vw["generative_2"]], [d2], G, G2, G1, G1, G2, G2, epi=EPI_SOFTPLUS,
+                 bias=[vb["generative_2"]])
+            gemm([d2], [vw["gen_mean"]], [r], G, W2, G2, G2, W2, W2, epi=EPI_SIGMOID_NOISE,
+                 bias=[vb["gen_mean"]], aux=[eps["eps_x"][t]], ldaux=W2, aux_scale=lik_std)
+            _ops.bernoulli_threshold_(r, eps["u_x"][t], win, G * W2)
+            ops.stn_forward(win, st_back[t], (C, C), out=canvas, z=zval, mask=zmask,
+                            accumulate=True)
+        Tx = int(live[:T].sum().item())  # the one readback: the reference's executed steps
+        self.generated_st_back = st_back[:Tx].transpose(0, 1).reshape(G, Tx, 2, 3)
+        self.generated_num_digits = digits
+        self.generated_samples = canvas.reshape(G, C, C, 1)
+        return self.generated_samples

@@ -415,14 +415,14 @@ def train_loop_asr(args, train_model, test_model, tr_x, tr_k, test, canvas, log,
     summary_folder = os.path.join(os.path.dirname(os.path.normpath(models_folder)), "summary")
     vis_n = args.test_batch if getattr(args, "test_batch", 0) > 0 else len(test[1])
 
-    def save_images(tag):
-        # train_air_pr.py:362-389 (the ASR generation grids need the
-        # generative LSTM prior, not part of this build)
+    def save_images(tag, gen_tag=None):
+        # train_air_pr.py:362-398: the reconstruction grids and one pair of
+        # generation grids (the model's loop draws the counts)
         if not ctx.main or getattr(args, "no_images", False):
             return
         from .visualize import save_visualizations
         save_visualizations(test_model, test[0][:vis_n], test[1][:vis_n], summary_folder, tag,
-                            num=NUM_IMAGES_TO_SAVE, generations=False)
+                            digits=None, num=NUM_IMAGES_TO_SAVE, gen_tag=gen_tag)
 
     log.info("Training...\n")
     try:
@@ -453,7 +453,8 @@ def train_loop_asr(args, train_model, test_model, tr_x, tr_k, test, canvas, log,
                 raise StopIteration
     except StopIteration:
         test_and_log(step)  # the reference logs the step here too (train_air_pr.py:426-430)
-        save_images("final")
+        # the final generation grids are tagged with the step (train_air_pr.py:462-469)
+        save_images("final", gen_tag=step)
         log.info("Final Best: elbo:{}\taccu:{}\tmse:{}\tiou:{}".format(*best))
         log.info("\ntraining has ended\n")
     return step

@@ -127,9 +127,12 @@ def reconstruction_images(model, images, zoom: int = 2, num: Optional[int] = Non
 
 def generation_images(model, num_steps: int, zoom: int = 2):
     """``generated_samples`` and ``generated_samples_bbox`` (air_model.py:1001-1146):
-    ([G, C, C, 1] canvas, [G, zC, zC, 3] enlarged canvas with windows)."""
+    ([G, C, C, 1] canvas, [G, zC, zC, 3] enlarged canvas with windows).
+    ``num_steps=None``: a model whose generation loop draws the count itself
+    (AIR-ASR, air_number_bbox_location.py:1124-1361): ``model.generate()``."""
     C = model.canvas_size
-    canvas = model.generate(num_steps).reshape(-1, C, C).float().cpu().numpy()
+    out = model.generate() if num_steps is None else model.generate(num_steps)
+    canvas = out.reshape(-1, C, C).float().cpu().numpy()
     G = canvas.shape[0]
     st = model.generated_st_back                             # [G, T, 2, 3]
     T = model.max_steps
@@ -145,7 +148,10 @@ def save_visualizations(model, images, targets, folder: str, tag, digits=(), num
     """training_air_original.py:368-411 for one test batch: visualize_{tag}.png
     (first ``num``), visualize_{tag}_wrong.png (misclassified, up to 100) and,
     per digit count i, visualize_gen{gen_tag}_{i}.png / visualize_genbbox{gen_tag}_{i}.png
-    (gen_tag defaults to tag; the final dump uses the step number there)."""
+    (gen_tag defaults to tag; the final dump uses the step number there).
+    ``digits=None``: the AIR-ASR model, whose generation draws its own counts:
+    one pair visualize_gen{gen_tag}.png / visualize_genbbox{gen_tag}.png
+    (train_air_pr.py:388-398)."""
     model.infer(images, targets)
     allv = reconstruction_images(model, images)
     pile_image(allv[:num], os.path.join(folder, "visualize_{}.png".format(tag)))
@@ -155,8 +161,13 @@ def save_visualizations(model, images, targets, folder: str, tag, digits=(), num
         pile_image(wrong[:100], os.path.join(folder, "visualize_{}_wrong.png".format(tag)))
     if not generations:
         return
+    gt = tag if gen_tag is None else gen_tag
+    if digits is None:
+        gen, gen_box = generation_images(model, None)
+        pile_image(gen, os.path.join(folder, "visualize_gen{}.png".format(gt)))
+        pile_image(gen_box, os.path.join(folder, "visualize_genbbox{}.png".format(gt)))
+        return
     for i in digits:
         gen, gen_box = generation_images(model, int(i))
-        gt = tag if gen_tag is None else gen_tag
         pile_image(gen, os.path.join(folder, "visualize_gen{}_{}.png".format(gt, i)))
         pile_image(gen_box, os.path.join(folder, "visualize_genbbox{}_{}.png".format(gt, i)))
