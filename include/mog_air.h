@@ -482,9 +482,11 @@ int mog_generation_prior(int G, int Z, float s_pm, float s_plv, float h_pm, floa
                          float* z, void* stream);
 
 /* ---- AIR-ASR cells and structural losses (air_number_bbox_location.py) ----
- * Record layout rec[step][28][B]: sm0 sm1 slv0 slv1 sl0 sl1 cm clv cl s tx ty
+ * Record layout rec[step][30][B]: sm0 sm1 slv0 slv1 sl0 sl1 cm clv cl s tx ty
  * gsm0 gsm1 gslv0 gslv1 plo lo y z act_old act live zkl skl shkl prn zprob
- * (zkl / skl / shkl masked as the reference's tf.where, prn live-gated).
+ * gcm gclv (zkl / skl / shkl masked as the reference's tf.where, prn
+ * live-gated; slots 28 / 29, the learned scale prior's mean and log-variance,
+ * are written and read by the *_learned entry points only).
  * w[20] (TF [in,out] layout): inf_shift dense_1 W,b, dense_3 W,b; inf_scale
  * dense W,b [258,64], dense_1 W,b [66,1], dense_2 W,b, dense_3 W,b; gen_shift
  * dense_1 W,b, dense_3 W,b; z_pres prior dense_1 W,b; z_pres log-odds
@@ -492,7 +494,13 @@ int mog_generation_prior(int G, int Z, float s_pm, float s_plv, float h_pm, floa
  * log-odds, gen_shift m / v, z_pres prior (null with fix_steps >= 0), and the
  * inf_scale m / v chains over h (finished in place: + shift latent terms,
  * bias, relu).  gammas[8] = num, margin, element, bbox, size, area, area_min,
- * area_max.  T <= 8 steps, <= 8 allowed counts. */
+ * area_max.  T <= 8 steps, <= 8 allowed counts.
+ * Learned scale prior (fix_scale_distribution=False, :482-509, :729-746; the
+ * *_learned entry points): gw[8] = gen_scale dense W,b [258,64], dense_1 W,b
+ * [66,1], dense_2 W,b, dense_3 W,b; hid / dpre have 10 entries, 8 / 9 the
+ * gen_scale m / v chains over hg (finished in place like 6 / 7); the scale KL
+ * is taken against N(gcm, exp(gclv)) from those heads per image instead of
+ * the constant scale_prior_*; douts has 14 columns (+ d gcm, d gclv). */
 /* U rows [z (Z) | ss (3) | h (H) | 0] of the two LSTMCell inputs (:403-412,
  * :457-463); null sources read as zeros.  out2 != NULL: the second cell's rows
  * [z | ss | h2 | 0] into out2 in the same launch. */
@@ -518,10 +526,18 @@ int mog_asr_step_forward(int B, int step, int train, int fix_steps, float thr, f
                          float* stop, int* digits, int* live, float* rec, float* theta_fwd,
                          float* theta_back, float* ss, float* scale, float* shift, float* zprob,
                          float* zmask, float* zval, float* zc, void* stream);
+int mog_asr_step_forward_learned(int B, int step, int train, int fix_steps, float thr,
+                                 float temperature, float gamma_num, const float* const* w,
+                                 const float* const* gw, float* const* hid,
+                                 const float* eps_shift, const float* eps_scale, const float* u,
+                                 float* stop, int* digits, int* live, float* rec,
+                                 float* theta_fwd, float* theta_back, float* ss, float* scale,
+                                 float* shift, float* zprob, float* zmask, float* zval, float* zc,
+                                 void* stream);
 /* per image KL sums (klsum, the reconstruction kernel's runloss), pr_loss
  * and its area / out / size / overlap terms over the executed steps; zsum[t]
  * = sum_b z_pres_prob (to be all-reduced over ranks for the margin loss)
- * (:917-935, :1017-1069).  rec [T][28][B], vkl / zmask [T][B]. */
+ * (:917-935, :1017-1069).  rec [T][30][B], vkl / zmask [T][B]. */
 int mog_asr_terms(int B, int T, int C, int nc, const int* cons, const float* gammas,
                   const float* rec, const float* vkl, const float* zmask, const int* live,
                   float* klsum, float* pr, float* area, float* out, float* size, float* overlap,
@@ -545,6 +561,15 @@ int mog_asr_step_backward(int B, int train, int fix_steps, float temperature,
                           const float* eps_shift, const float* eps_scale, const float* dtheta_fwd,
                           const float* dtheta_back, const float* dot, const float* dreg,
                           const float* dss, float* douts, float* const* dpre, void* stream);
+/* the same for mog_asr_step_forward_learned: douts [B][14] (+ gcm gclv),
+ * dpre[10] */
+int mog_asr_step_backward_learned(int B, int train, int fix_steps, float temperature,
+                                  float grad_scale, const float* const* w,
+                                  const float* const* gw, float* const* hid, const float* rec,
+                                  const float* eps_shift, const float* eps_scale,
+                                  const float* dtheta_fwd, const float* dtheta_back,
+                                  const float* dot, const float* dreg, const float* dss,
+                                  float* douts, float* const* dpre, void* stream);
 
 /* ---- AIR-ASR generation (air_number_bbox_location.py:1124-1361) ----------
  * One step of the generation loop for G images, after the generative
@@ -567,6 +592,19 @@ int mog_asr_gen_step(int G, int Z, int step, int fix_steps, float thr, float tem
                      const float* eps_z, const float* u, float* stop, int* digits, int* live,
                      float* ss, float* z, float* theta_back, float* zval, float* zmask,
                      void* stream);
+/* The same with the learned scale prior (:1170-1201): ghid[2] [G,64] = the
+ * gen_scale dense / dense_2 chains over the new output hg (raw: a GEMM from
+ * +0 without bias), gw[8] as mog_asr_step_forward_learned.  The kernel adds
+ * the generated shift latent's two terms, bias and relu, runs the 66-term
+ * output chains, and draws scale latent = gcm + eps_scale sqrt(exp(gclv)). */
+int mog_asr_gen_step_learned(int G, int Z, int step, int fix_steps, float thr, float temperature,
+                             float s, float vae_prior_mean, float vae_prior_logvar,
+                             const float* const* w, const float* const* hid,
+                             const float* const* gw, const float* const* ghid,
+                             const float* eps_shift, const float* eps_scale, const float* eps_z,
+                             const float* u, float* stop, int* digits, int* live, float* ss,
+                             float* z, float* theta_back, float* zval, float* zmask,
+                             void* stream);
 /* out[i] = x[i] > u[i] ? 1 : 0 for n floats: the Bernoulli sample of the
  * decoded window (vae.py:83-84 relu(sign(samples - U))).  16-byte vector
  * accesses when x, u and out are 16-byte aligned; out may be x or u. */

@@ -14,9 +14,11 @@ namespace {
 enum {
   Q_SM0, Q_SM1, Q_SLV0, Q_SLV1, Q_SL0, Q_SL1, Q_CM, Q_CLV, Q_CL, Q_S, Q_TX, Q_TY,
   Q_GSM0, Q_GSM1, Q_GSLV0, Q_GSLV1, Q_PLO, Q_LO, Q_Y, Q_Z, Q_ACT_OLD, Q_ACT, Q_LIVE,
-  Q_ZKL, Q_SKL, Q_SHKL, Q_PRN, Q_ZPROB, Q_N
+  Q_ZKL, Q_SKL, Q_SHKL, Q_PRN, Q_ZPROB, Q_GCM, Q_GCLV, Q_N
 };
-static_assert(Q_N == 28, "record layout is part of the ABI (include/mog_air.h)");
+static_assert(Q_N == 30 && Q_GCM == 28, "record layout is part of the ABI (include/mog_air.h)");
+// slots the fixed scale prior writes (Q_GCM / Q_GCLV: the learned prior's per-image values)
+constexpr int Q_FIXED = Q_GCM;
 
 // output-layer weights (TF [in, out]) in the ABI order of w[20]
 enum {
@@ -28,9 +30,17 @@ enum {
   W_N
 };
 
-// douts slots ([B][12] per step): gradients wrt the output-layer values
+// gen_scale weights (learned scale prior; TF [in, out]) in the ABI order of gw[8]
+enum {
+  W_GC0, B_GC0, W_GC1, B_GC1,            // gen_scale dense [258,64] / dense_1 [66,1]
+  W_GC2, B_GC2, W_GC3, B_GC3,            // gen_scale dense_2 / dense_3
+  GW_N
+};
+
+// douts slots ([B][12] per step, [B][14] with the learned scale prior):
+// gradients wrt the output-layer values
 enum { D_SM0, D_SM1, D_SLV0, D_SLV1, D_LO, D_GSM0, D_GSM1, D_GSLV0, D_GSLV1, D_PLO, D_CM,
-       D_CLV, D_N };
+       D_CLV, D_N, D_GCM = D_N, D_GCLV, D_NL };
 
 struct AsrCfg {
   int B, step, train, fix_steps;
@@ -40,9 +50,13 @@ struct AsrCfg {
 struct AsrW {
   const float* w[W_N];
 };
+struct AsrGW {
+  const float* w[GW_N];  // null with the fixed scale prior
+};
 struct AsrHid {
-  float* h[8];  // [B,64]: 0 inf_shift m, 1 inf_shift v, 2 z_pres log-odds, 3 gen_shift m,
-                // 4 gen_shift v, 5 z_pres prior (or null), 6/7 inf_scale m/v (raw -> finished)
+  float* h[10];  // [B,64]: 0 inf_shift m, 1 inf_shift v, 2 z_pres log-odds, 3 gen_shift m,
+                 // 4 gen_shift v, 5 z_pres prior (or null), 6/7 inf_scale m/v (raw -> finished),
+                 // 8/9 gen_scale m/v (raw -> finished; null with the fixed scale prior)
 };
 
 constexpr int HS = 64;
@@ -168,11 +182,16 @@ struct AsrFwdIO {
 // One wave per image (4 per block): head output chains, latent sampling, the
 // scale hidden layers finished over the shift latent, theta / theta^-1,
 // concrete z_pres, KLs, entropy regulariser, stopping sum, counts, live flag.
-__global__ __launch_bounds__(256) void asr_step_fwd_kernel(AsrCfg cfg, AsrW W, AsrHid hp,
-                                                           AsrFwdIO io) {
+// LearnedScale (fix_scale_distribution=False, :482-509, :729-746): the scale
+// prior is the gen_scale heads on concat([hg, shift_latent]) instead of the
+// constant N(gcm, gcvar); it enters only the scale KL.
+template <bool LearnedScale>
+__global__ __launch_bounds__(256) void asr_step_fwd_kernel(AsrCfg cfg, AsrW W, AsrGW GW,
+                                                           AsrHid hp, AsrFwdIO io) {
 #pragma clang fp contract(off)
   __shared__ float sv[4][16];
   __shared__ float sh6[4][HS], sh7[4][HS];
+  __shared__ float sh8[LearnedScale ? 4 : 1][HS], sh9[LearnedScale ? 4 : 1][HS];
   const int m = threadIdx.x >> 6, q = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + m;
   const int B = cfg.B;
@@ -188,6 +207,12 @@ __global__ __launch_bounds__(256) void asr_step_fwd_kernel(AsrCfg cfg, AsrW W, A
   const float w7a = W.w[W_IC2][256 * HS + q], w7b = W.w[W_IC2][257 * HS + q], b7 = W.w[B_IC2][q];
   const float e_s = io.eps_scale[bc], uu = io.u[bc], stop_old = io.stop[bc];
   const int live = io.live[cfg.step], dig = io.digits[bc];
+  float h8 = 0.0f, h9 = 0.0f, w8a = 0.0f, w8b = 0.0f, b8 = 0.0f, w9a = 0.0f, w9b = 0.0f, b9 = 0.0f;
+  if constexpr (LearnedScale) {
+    h8 = hp.h[8][r6]; h9 = hp.h[9][r6];
+    w8a = GW.w[W_GC0][256 * HS + q]; w8b = GW.w[W_GC0][257 * HS + q]; b8 = GW.w[B_GC0][q];
+    w9a = GW.w[W_GC2][256 * HS + q]; w9b = GW.w[W_GC2][257 * HS + q]; b9 = GW.w[B_GC2][q];
+  }
   // phase 1: ten output-layer chains over the 64 hidden units
   if (q < 10) {
     float v = 0.0f;
@@ -230,13 +255,30 @@ __global__ __launch_bounds__(256) void asr_step_fwd_kernel(AsrCfg cfg, AsrW W, A
     a7 = a7 + b7;
     sh6[m][q] = a6 > 0.0f ? a6 : 0.0f;
     sh7[m][q] = a7 > 0.0f ? a7 : 0.0f;
+    if constexpr (LearnedScale) {
+      // gen_scale hidden layers on concat([hg, shift_latent]) (:482-499), likewise
+      float a8 = h8, a9 = h9;
+      a8 = fmaf(sl0, w8a, a8);
+      a8 = fmaf(sl1, w8b, a8);
+      a8 = a8 + b8;
+      a9 = fmaf(sl0, w9a, a9);
+      a9 = fmaf(sl1, w9b, a9);
+      a9 = a9 + b9;
+      sh8[m][q] = a8 > 0.0f ? a8 : 0.0f;
+      sh9[m][q] = a9 > 0.0f ? a9 : 0.0f;
+    }
   }
   __syncthreads();
   if (ok) {
     hp.h[6][r6] = sh6[m][q];
     hp.h[7][r6] = sh7[m][q];
+    if constexpr (LearnedScale) {
+      hp.h[8][r6] = sh8[m][q];
+      hp.h[9][r6] = sh9[m][q];
+    }
   }
   // phase 4: scale mean / log-variance on concat([hidden, shift_latent])
+  // (lanes 2 / 3: the learned prior's, :501-509)
   if (q < 2) {
     const float* hh = q == 0 ? sh6[m] : sh7[m];
     const float* w = W.w[q == 0 ? W_IC1 : W_IC3];
@@ -244,6 +286,16 @@ __global__ __launch_bounds__(256) void asr_step_fwd_kernel(AsrCfg cfg, AsrW W, A
     acc = fmaf(sl0, w[HS], acc);
     acc = fmaf(sl1, w[HS + 1], acc);
     sv[m][12 + q] = acc + W.w[q == 0 ? B_IC1 : B_IC3][0];
+  }
+  if constexpr (LearnedScale) {
+    if (q == 2 || q == 3) {
+      const float* hh = q == 2 ? sh8[m] : sh9[m];
+      const float* w = GW.w[q == 2 ? W_GC1 : W_GC3];
+      float acc = chain64(hh, w, 1);
+      acc = fmaf(sl0, w[HS], acc);
+      acc = fmaf(sl1, w[HS + 1], acc);
+      sv[m][12 + q] = acc + GW.w[q == 2 ? B_GC1 : B_GC3][0];
+    }
   }
   __syncthreads();
   if (q != 0 || !ok) return;
@@ -294,8 +346,14 @@ __global__ __launch_bounds__(256) void asr_step_fwd_kernel(AsrCfg cfg, AsrW W, A
     io.live[cfg.step + 1] = 1;
   }
   // scale / shift KLs with the NEW stopping sum (:728-765)
-  const float dc = cm - cfg.gcm;
-  const float skl = 0.5f * ((((cfg.gclv - clv) - 1.0f) + cvar / cfg.gcvar) + (dc * dc) / cfg.gcvar);
+  float gcm = cfg.gcm, gcvar = cfg.gcvar, gclv = cfg.gclv;
+  if constexpr (LearnedScale) {
+    gcm = sv[m][14];
+    gclv = sv[m][15];
+    gcvar = mog_expf(gclv);
+  }
+  const float dc = cm - gcm;
+  const float skl = 0.5f * ((((gclv - clv) - 1.0f) + cvar / gcvar) + (dc * dc) / gcvar);
   float shs = 0.0f;
   {
     const float gsm[2] = {gsm0, gsm1}, gslv[2] = {gslv0, gslv1};
@@ -315,9 +373,9 @@ __global__ __launch_bounds__(256) void asr_step_fwd_kernel(AsrCfg cfg, AsrW W, A
                          gsm0, gsm1, gslv0, gslv1, plo, lo, y, z,
                          act_old ? 1.0f : 0.0f, act ? 1.0f : 0.0f, live ? 1.0f : 0.0f,
                          act_old ? zkl : 0.0f, act ? skl : 0.0f, act ? 0.5f * shs : 0.0f,
-                         live ? prn : 0.0f, zprob};
+                         live ? prn : 0.0f, zprob, gcm, gclv};
 #pragma unroll
-  for (int k = 0; k < Q_N; ++k) rr[(size_t)k * B + b] = rv[k];
+  for (int k = 0; k < (LearnedScale ? Q_N : Q_FIXED); ++k) rr[(size_t)k * B + b] = rv[k];
 }
 
 struct AsrLossCfg {
@@ -588,14 +646,16 @@ struct AsrBwdIO {
   const float* dot;          // [B] sum_p dcanvas * w
   const float* dreg;         // [4, B] regulariser gradients of this step
   const float* dss;          // [B,3] carry from the next step's LSTM inputs (or null)
-  float* douts;              // [B, D_N]
-  float* dpre[8];            // [B,64] pre-activation gradients of the hidden layers
+  float* douts;              // [B, D_N] ([B, D_NL] with the learned scale prior)
+  float* dpre[10];           // [B,64] pre-activation gradients of the hidden layers
 };
 
 // One wave per image: backward of asr_step_fwd_kernel.
-__global__ __launch_bounds__(256) void asr_step_bwd_kernel(AsrCfg cfg, AsrW W, AsrHid hp,
-                                                           AsrBwdIO io) {
+template <bool LearnedScale>
+__global__ __launch_bounds__(256) void asr_step_bwd_kernel(AsrCfg cfg, AsrW W, AsrGW GW,
+                                                           AsrHid hp, AsrBwdIO io) {
 #pragma clang fp contract(off)
+  constexpr int DN = LearnedScale ? D_NL : D_N;
   __shared__ float sv[4][16];
   const int m = threadIdx.x >> 6, q = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + m;
@@ -629,11 +689,22 @@ __global__ __launch_bounds__(256) void asr_step_bwd_kernel(AsrCfg cfg, AsrW W, A
     const float wn = act ? gL : 0.0f;
     const float cvar = mog_expf(clv);
     const float dcl = ds * s * (1.0f - s) + (io.dss ? io.dss[(size_t)bc * 3 + 2] : 0.0f);
-    const float dcm = dcl + wn * (cm - cfg.gcm) / cfg.gcvar;
+    float gcm = cfg.gcm, gcvar = cfg.gcvar;
+    if constexpr (LearnedScale) {
+      gcm = R(Q_GCM);
+      gcvar = mog_expf(R(Q_GCLV));
+    }
+    const float dcm = dcl + wn * (cm - gcm) / gcvar;
     const float dclv = dcl * io.eps_scale[bc] * 0.5f * sqrtf(cvar) +
-                       wn * 0.5f * (-1.0f + cvar / cfg.gcvar);
+                       wn * 0.5f * (-1.0f + cvar / gcvar);
     sv[m][0] = dtx; sv[m][1] = dty; sv[m][2] = dlo; sv[m][3] = dplo;
     sv[m][4] = dcm; sv[m][5] = dclv; sv[m][6] = wn;
+    if constexpr (LearnedScale) {
+      // the learned prior's mean / log-variance (the KL's second Gaussian)
+      const float dd = cm - gcm;
+      sv[m][7] = -wn * dd / gcvar;
+      sv[m][14] = wn * 0.5f * ((1.0f - cvar / gcvar) - (dd * dd) / gcvar);
+    }
   }
   __syncthreads();
   // scale hidden layers: dpre6/7 and their contribution to the shift latent
@@ -652,15 +723,36 @@ __global__ __launch_bounds__(256) void asr_step_bwd_kernel(AsrCfg cfg, AsrW W, A
   float p1 = d6 * W.w[W_IC0][257 * HS + q] + d7 * W.w[W_IC2][257 * HS + q];
   p0 = mog_wave_sum(p0);
   p1 = mog_wave_sum(p1);
+  float dgcm = 0.0f, dgclv = 0.0f, p2 = 0.0f, p3 = 0.0f;
+  if constexpr (LearnedScale) {
+    // gen_scale hidden layers: dpre8/9 and their contribution to the shift latent
+    dgcm = sv[m][7];
+    dgclv = sv[m][14];
+    const float w8 = GW.w[W_GC1][q], w9 = GW.w[W_GC3][q];
+    const float d8 = hp.h[8][rq] > 0.0f ? dgcm * w8 : 0.0f;
+    const float d9 = hp.h[9][rq] > 0.0f ? dgclv * w9 : 0.0f;
+    if (ok) {
+      io.dpre[8][rq] = d8;
+      io.dpre[9][rq] = d9;
+    }
+    p2 = d8 * GW.w[W_GC0][256 * HS + q] + d9 * GW.w[W_GC2][256 * HS + q];
+    p3 = d8 * GW.w[W_GC0][257 * HS + q] + d9 * GW.w[W_GC2][257 * HS + q];
+    p2 = mog_wave_sum(p2);
+    p3 = mog_wave_sum(p3);
+  }
   if (q == 0) {
     const float tx = R(Q_TX), ty = R(Q_TY), wn = sv[m][6];
     const float carry0 = io.dss ? io.dss[(size_t)bc * 3] : 0.0f;
     const float carry1 = io.dss ? io.dss[(size_t)bc * 3 + 1] : 0.0f;
-    const float dsl[2] = {
+    float dsl[2] = {
         sv[m][0] * (1.0f - tx * tx) + carry0 + dcm * W.w[W_IC1][HS] + dclv * W.w[W_IC3][HS] + p0,
         sv[m][1] * (1.0f - ty * ty) + carry1 + dcm * W.w[W_IC1][HS + 1] +
             dclv * W.w[W_IC3][HS + 1] + p1};
-    float o[D_N];
+    if constexpr (LearnedScale) {
+      dsl[0] += dgcm * GW.w[W_GC1][HS] + dgclv * GW.w[W_GC3][HS] + p2;
+      dsl[1] += dgcm * GW.w[W_GC1][HS + 1] + dgclv * GW.w[W_GC3][HS + 1] + p3;
+    }
+    float o[DN];
     for (int d = 0; d < 2; ++d) {
       const float sm = R(Q_SM0 + d), slv = R(Q_SLV0 + d);
       const float gsm = R(Q_GSM0 + d), gslv = R(Q_GSLV0 + d);
@@ -676,8 +768,12 @@ __global__ __launch_bounds__(256) void asr_step_bwd_kernel(AsrCfg cfg, AsrW W, A
     o[D_PLO] = sv[m][3];
     o[D_CM] = dcm;
     o[D_CLV] = dclv;
-    for (int k = 0; k < D_N; ++k)
-      if (ok) io.douts[(size_t)bc * D_N + k] = o[k];
+    if constexpr (LearnedScale) {
+      o[D_GCM] = dgcm;
+      o[D_GCLV] = dgclv;
+    }
+    for (int k = 0; k < DN; ++k)
+      if (ok) io.douts[(size_t)bc * DN + k] = o[k];
     sv[m][0] = o[D_SM0]; sv[m][1] = o[D_SM1]; sv[m][2] = o[D_SLV0]; sv[m][3] = o[D_SLV1];
     sv[m][8] = o[D_LO]; sv[m][9] = o[D_GSM0]; sv[m][10] = o[D_GSM1];
     sv[m][11] = o[D_GSLV0]; sv[m][12] = o[D_GSLV1]; sv[m][13] = o[D_PLO];
@@ -748,6 +844,47 @@ static int fill_w(AsrW& W, const float* const* w) {
   return 1;
 }
 
+static int fill_gw(AsrGW& GW, const float* const* gw) {
+  for (int i = 0; i < GW_N; ++i) {
+    if (!gw[i]) return 0;
+    GW.w[i] = gw[i];
+  }
+  return 1;
+}
+
+// gw == null: the fixed scale prior (hid[8]); else the learned one (hid[10])
+static int asr_step_forward(int B, int step, int train, int fix_steps, float thr,
+                            float temperature, float scale_prior_mean, float scale_prior_var,
+                            float scale_prior_logvar, float gamma_num, const float* const* w,
+                            const float* const* gw, float* const* hid, const float* eps_shift,
+                            const float* eps_scale, const float* u, float* stop, int* digits,
+                            int* live, float* rec, float* theta_fwd, float* theta_back,
+                            float* ss, float* scale, float* shift, float* zprob, float* zmask,
+                            float* zval, float* zc, void* stream) {
+  MOG_CHECK_ARG(B >= 0 && w && hid && eps_shift && eps_scale && u && stop && digits && live);
+  MOG_CHECK_ARG(rec && theta_fwd && theta_back && ss && scale && shift && zprob && zmask && zval &&
+                zc);
+  if (B == 0) return 0;
+  AsrCfg c{B, step, train, fix_steps, thr, temperature, scale_prior_mean, scale_prior_var,
+           scale_prior_logvar, gamma_num, 0.0f};
+  AsrW W;
+  MOG_CHECK_ARG(fill_w(W, w));
+  AsrGW GW{};
+  MOG_CHECK_ARG(!gw || fill_gw(GW, gw));
+  AsrHid hp{};
+  for (int i = 0; i < (gw ? 10 : 8); ++i) {
+    MOG_CHECK_ARG(hid[i] || (i == 5 && fix_steps >= 0));
+    hp.h[i] = hid[i];
+  }
+  AsrFwdIO io{eps_shift, eps_scale, u,     stop,  digits, live, rec, theta_fwd, theta_back,
+              ss,        scale,     shift, zprob, zmask, zval,   zc};
+  if (gw)
+    asr_step_fwd_kernel<true><<<mog_cdiv(B, 4), 256, 0, mog_stream(stream)>>>(c, W, GW, hp, io);
+  else
+    asr_step_fwd_kernel<false><<<mog_cdiv(B, 4), 256, 0, mog_stream(stream)>>>(c, W, GW, hp, io);
+  MOG_LAUNCH_RET();
+}
+
 extern "C" int mog_asr_step_forward(int B, int step, int train, int fix_steps, float thr,
                                     float temperature, float scale_prior_mean,
                                     float scale_prior_var, float scale_prior_logvar,
@@ -757,23 +894,25 @@ extern "C" int mog_asr_step_forward(int B, int step, int train, int fix_steps, f
                                     float* rec, float* theta_fwd, float* theta_back, float* ss,
                                     float* scale, float* shift, float* zprob, float* zmask,
                                     float* zval, float* zc, void* stream) {
-  MOG_CHECK_ARG(B >= 0 && w && hid && eps_shift && eps_scale && u && stop && digits && live);
-  MOG_CHECK_ARG(rec && theta_fwd && theta_back && ss && scale && shift && zprob && zmask && zval &&
-                zc);
-  if (B == 0) return 0;
-  AsrCfg c{B, step, train, fix_steps, thr, temperature, scale_prior_mean, scale_prior_var,
-           scale_prior_logvar, gamma_num, 0.0f};
-  AsrW W;
-  MOG_CHECK_ARG(fill_w(W, w));
-  AsrHid hp;
-  for (int i = 0; i < 8; ++i) {
-    MOG_CHECK_ARG(hid[i] || (i == 5 && fix_steps >= 0));
-    hp.h[i] = hid[i];
-  }
-  AsrFwdIO io{eps_shift, eps_scale, u,     stop,  digits, live, rec, theta_fwd, theta_back,
-              ss,        scale,     shift, zprob, zmask, zval,   zc};
-  asr_step_fwd_kernel<<<mog_cdiv(B, 4), 256, 0, mog_stream(stream)>>>(c, W, hp, io);
-  MOG_LAUNCH_RET();
+  return asr_step_forward(B, step, train, fix_steps, thr, temperature, scale_prior_mean,
+                          scale_prior_var, scale_prior_logvar, gamma_num, w, nullptr, hid,
+                          eps_shift, eps_scale, u, stop, digits, live, rec, theta_fwd, theta_back,
+                          ss, scale, shift, zprob, zmask, zval, zc, stream);
+}
+
+extern "C" int mog_asr_step_forward_learned(int B, int step, int train, int fix_steps, float thr,
+                                            float temperature, float gamma_num,
+                                            const float* const* w, const float* const* gw,
+                                            float* const* hid, const float* eps_shift,
+                                            const float* eps_scale, const float* u, float* stop,
+                                            int* digits, int* live, float* rec, float* theta_fwd,
+                                            float* theta_back, float* ss, float* scale,
+                                            float* shift, float* zprob, float* zmask, float* zval,
+                                            float* zc, void* stream) {
+  MOG_CHECK_ARG(gw);
+  return asr_step_forward(B, step, train, fix_steps, thr, temperature, 0.0f, 1.0f, 0.0f, gamma_num,
+                          w, gw, hid, eps_shift, eps_scale, u, stop, digits, live, rec, theta_fwd,
+                          theta_back, ss, scale, shift, zprob, zmask, zval, zc, stream);
 }
 
 static int fill_loss_cfg(AsrLossCfg& c, int B, int T, int C, int nc, const int* cons,
@@ -827,6 +966,38 @@ extern "C" int mog_asr_terms_backward(int B, int T, int C, int nc, const int* co
   MOG_LAUNCH_RET();
 }
 
+static int asr_step_backward(int B, int train, int fix_steps, float temperature,
+                             float scale_prior_mean, float scale_prior_var, float grad_scale,
+                             const float* const* w, const float* const* gw, float* const* hid,
+                             const float* rec, const float* eps_shift, const float* eps_scale,
+                             const float* dtheta_fwd, const float* dtheta_back, const float* dot,
+                             const float* dreg, const float* dss, float* douts,
+                             float* const* dpre, void* stream) {
+  MOG_CHECK_ARG(B >= 0 && w && hid && rec && eps_shift && eps_scale && dtheta_fwd && dtheta_back);
+  MOG_CHECK_ARG(dot && dreg && douts && dpre);
+  if (B == 0) return 0;
+  AsrCfg c{B, 0, train, fix_steps, 0.0f, temperature, scale_prior_mean, scale_prior_var, 0.0f,
+           0.0f, grad_scale};
+  AsrW W;
+  MOG_CHECK_ARG(fill_w(W, w));
+  AsrGW GW{};
+  MOG_CHECK_ARG(!gw || fill_gw(GW, gw));
+  AsrHid hp{};
+  AsrBwdIO io{};
+  io.rec = rec; io.eps_shift = eps_shift; io.eps_scale = eps_scale; io.dtheta_fwd = dtheta_fwd;
+  io.dtheta_back = dtheta_back; io.dot = dot; io.dreg = dreg; io.dss = dss; io.douts = douts;
+  for (int i = 0; i < (gw ? 10 : 8); ++i) {
+    MOG_CHECK_ARG((hid[i] && dpre[i]) || (i == 5 && fix_steps >= 0));
+    hp.h[i] = hid[i];
+    io.dpre[i] = dpre[i];
+  }
+  if (gw)
+    asr_step_bwd_kernel<true><<<mog_cdiv(B, 4), 256, 0, mog_stream(stream)>>>(c, W, GW, hp, io);
+  else
+    asr_step_bwd_kernel<false><<<mog_cdiv(B, 4), 256, 0, mog_stream(stream)>>>(c, W, GW, hp, io);
+  MOG_LAUNCH_RET();
+}
+
 extern "C" int mog_asr_step_backward(int B, int train, int fix_steps, float temperature,
                                      float scale_prior_mean, float scale_prior_var,
                                      float grad_scale, const float* const* w,
@@ -835,22 +1006,21 @@ extern "C" int mog_asr_step_backward(int B, int train, int fix_steps, float temp
                                      const float* dtheta_back, const float* dot,
                                      const float* dreg, const float* dss, float* douts,
                                      float* const* dpre, void* stream) {
-  MOG_CHECK_ARG(B >= 0 && w && hid && rec && eps_shift && eps_scale && dtheta_fwd && dtheta_back);
-  MOG_CHECK_ARG(dot && dreg && douts && dpre);
-  if (B == 0) return 0;
-  AsrCfg c{B, 0, train, fix_steps, 0.0f, temperature, scale_prior_mean, scale_prior_var, 0.0f,
-           0.0f, grad_scale};
-  AsrW W;
-  MOG_CHECK_ARG(fill_w(W, w));
-  AsrHid hp;
-  AsrBwdIO io;
-  io.rec = rec; io.eps_shift = eps_shift; io.eps_scale = eps_scale; io.dtheta_fwd = dtheta_fwd;
-  io.dtheta_back = dtheta_back; io.dot = dot; io.dreg = dreg; io.dss = dss; io.douts = douts;
-  for (int i = 0; i < 8; ++i) {
-    MOG_CHECK_ARG((hid[i] && dpre[i]) || (i == 5 && fix_steps >= 0));
-    hp.h[i] = hid[i];
-    io.dpre[i] = dpre[i];
-  }
-  asr_step_bwd_kernel<<<mog_cdiv(B, 4), 256, 0, mog_stream(stream)>>>(c, W, hp, io);
-  MOG_LAUNCH_RET();
+  return asr_step_backward(B, train, fix_steps, temperature, scale_prior_mean, scale_prior_var,
+                           grad_scale, w, nullptr, hid, rec, eps_shift, eps_scale, dtheta_fwd,
+                           dtheta_back, dot, dreg, dss, douts, dpre, stream);
+}
+
+extern "C" int mog_asr_step_backward_learned(int B, int train, int fix_steps, float temperature,
+                                             float grad_scale, const float* const* w,
+                                             const float* const* gw, float* const* hid,
+                                             const float* rec, const float* eps_shift,
+                                             const float* eps_scale, const float* dtheta_fwd,
+                                             const float* dtheta_back, const float* dot,
+                                             const float* dreg, const float* dss, float* douts,
+                                             float* const* dpre, void* stream) {
+  MOG_CHECK_ARG(gw);
+  return asr_step_backward(B, train, fix_steps, temperature, 0.0f, 1.0f, grad_scale, w, gw, hid,
+                           rec, eps_shift, eps_scale, dtheta_fwd, dtheta_back, dot, dreg, dss,
+                           douts, dpre, stream);
 }

@@ -54,14 +54,23 @@ struct GenIO {
   float* theta_back;       // [G,6]
   float* zval;             // [G]
   float* zmask;            // [G]
+  // learned scale prior (null with the fixed one)
+  const float* hid_gm;     // [G,64] gen_scale/dense chain over hg (raw: no latent terms / bias)
+  const float* hid_gv;     // [G,64] gen_scale/dense_2 likewise
+  const float* gw[8];      // gen_scale dense W,b [258,64], dense_1 W,b [66,1], dense_2, dense_3
 };
 
 // One wave per image (4 per block), as asr_step_fwd_kernel: lanes 0..4 run the
 // five output-layer chains, every lane draws its latent elements, lane 0
-// finishes the image.
+// finishes the image.  LearnedScale (fix_scale_distribution=False,
+// :1170-1201): every lane finishes its unit of the two gen_scale hidden layers
+// on the generated shift latent, lanes 0 / 1 run the output chains, and the
+// scale latent is drawn from that Gaussian.
+template <bool LearnedScale>
 __global__ __launch_bounds__(256) void asr_gen_step_kernel(GenCfg cfg, GenIO io) {
 #pragma clang fp contract(off)
   __shared__ float sv[4][8];
+  __shared__ float sh8[LearnedScale ? 4 : 1][HS], sh9[LearnedScale ? 4 : 1][HS];
   const int m = threadIdx.x >> 6, q = threadIdx.x & 63;
   const int g = blockIdx.x * 4 + m;
   const bool ok = g < cfg.G;
@@ -73,6 +82,13 @@ __global__ __launch_bounds__(256) void asr_gen_step_kernel(GenCfg cfg, GenIO io)
   const float e_s = io.eps_scale[gc], uu = io.u[gc], stop_old = io.stop[gc];
   const int dig = io.digits[gc];
   const float ez = q < Z ? io.eps_z[(size_t)gc * Z + q] : 0.0f;
+  float h8 = 0.0f, h9 = 0.0f, w8a = 0.0f, w8b = 0.0f, b8 = 0.0f, w9a = 0.0f, w9b = 0.0f, b9 = 0.0f;
+  if constexpr (LearnedScale) {
+    const size_t rq = (size_t)gc * HS + q;
+    h8 = io.hid_gm[rq]; h9 = io.hid_gv[rq];
+    w8a = io.gw[0][256 * HS + q]; w8b = io.gw[0][257 * HS + q]; b8 = io.gw[1][q];
+    w9a = io.gw[4][256 * HS + q]; w9b = io.gw[4][257 * HS + q]; b9 = io.gw[5][q];
+  }
   if (q < 5) {
     const size_t r = (size_t)gc * HS;
     float v;
@@ -88,6 +104,33 @@ __global__ __launch_bounds__(256) void asr_gen_step_kernel(GenCfg cfg, GenIO io)
     sv[m][q] = v;
   }
   __syncthreads();
+  float gcm = 0.0f, gclv = 0.0f;
+  if constexpr (LearnedScale) {
+    // every lane the shift latent (the same bits), then its hidden unit
+    const float l0 = sv[m][0] + es0 * sqrtf(mog_expf(sv[m][2]));
+    const float l1 = sv[m][1] + es1 * sqrtf(mog_expf(sv[m][3]));
+    float a8 = h8, a9 = h9;
+    a8 = fmaf(l0, w8a, a8);
+    a8 = fmaf(l1, w8b, a8);
+    a8 = a8 + b8;
+    a9 = fmaf(l0, w9a, a9);
+    a9 = fmaf(l1, w9b, a9);
+    a9 = a9 + b9;
+    sh8[m][q] = a8 > 0.0f ? a8 : 0.0f;
+    sh9[m][q] = a9 > 0.0f ? a9 : 0.0f;
+    __syncthreads();
+    if (q < 2) {
+      const float* hh = q == 0 ? sh8[m] : sh9[m];
+      const float* w = io.gw[q == 0 ? 2 : 6];
+      float acc = chain64(hh, w, 1);
+      acc = fmaf(l0, w[HS], acc);
+      acc = fmaf(l1, w[HS + 1], acc);
+      sv[m][5 + q] = acc + io.gw[q == 0 ? 3 : 7][0];
+    }
+    __syncthreads();
+    gcm = sv[m][5];
+    gclv = sv[m][6];
+  }
   if (!ok) return;
   // latent (vae.py:63-66): every lane its elements
   const float zsd = sqrtf(mog_expf(cfg.vae_prior_logvar));
@@ -100,7 +143,8 @@ __global__ __launch_bounds__(256) void asr_gen_step_kernel(GenCfg cfg, GenIO io)
   const float sl0 = sv[m][0] + es0 * sqrtf(mog_expf(sv[m][2]));
   const float sl1 = sv[m][1] + es1 * sqrtf(mog_expf(sv[m][3]));
   const float tx = mog_tanhf(sl0), ty = mog_tanhf(sl1);
-  const float cl = cfg.scale_prior_mean + e_s * sqrtf(cfg.scale_prior_var);
+  float cl = cfg.scale_prior_mean + e_s * sqrtf(cfg.scale_prior_var);
+  if constexpr (LearnedScale) cl = gcm + e_s * sqrtf(mog_expf(gclv));
   const float s = cfg.s;
   float* tb = io.theta_back + (size_t)g * 6;
   tb[0] = 1.0f / s; tb[1] = 0.0f; tb[2] = -tx / s; tb[3] = 0.0f; tb[4] = 1.0f / s; tb[5] = -ty / s;
@@ -147,14 +191,15 @@ __global__ __launch_bounds__(256) void bernoulli_threshold_kernel(const float* x
 
 }  // namespace
 
-extern "C" int mog_asr_gen_step(int G, int Z, int step, int fix_steps, float thr,
-                                float temperature, float scale_prior_mean, float scale_prior_var,
-                                float s, float vae_prior_mean, float vae_prior_logvar,
-                                const float* const* w, const float* const* hid,
-                                const float* eps_shift, const float* eps_scale,
-                                const float* eps_z, const float* u, float* stop, int* digits,
-                                int* live, float* ss, float* z, float* theta_back, float* zval,
-                                float* zmask, void* stream) {
+// gw == null: the fixed scale prior; else gw[8] / ghid[2] of the learned one
+static int asr_gen_step(int G, int Z, int step, int fix_steps, float thr, float temperature,
+                        float scale_prior_mean, float scale_prior_var, float s,
+                        float vae_prior_mean, float vae_prior_logvar, const float* const* w,
+                        const float* const* hid, const float* const* gw,
+                        const float* const* ghid, const float* eps_shift, const float* eps_scale,
+                        const float* eps_z, const float* u, float* stop, int* digits, int* live,
+                        float* ss, float* z, float* theta_back, float* zval, float* zmask,
+                        void* stream) {
   MOG_CHECK_ARG(G >= 0 && Z > 0 && step >= 0 && s > 0.0f && w && hid && eps_shift && eps_scale && eps_z && u);
   MOG_CHECK_ARG(stop && digits && live && ss && z && theta_back && zval && zmask);
   MOG_CHECK_ARG(hid[0] && hid[1] && (hid[2] || fix_steps >= 0));
@@ -170,8 +215,47 @@ extern "C" int mog_asr_gen_step(int G, int Z, int step, int fix_steps, float thr
   io.eps_shift = eps_shift; io.eps_scale = eps_scale; io.eps_z = eps_z; io.u = u;
   io.stop = stop; io.digits = digits; io.live = live; io.ss = ss; io.z = z;
   io.theta_back = theta_back; io.zval = zval; io.zmask = zmask;
-  asr_gen_step_kernel<<<mog_cdiv(G, 4), 256, 0, mog_stream(stream)>>>(c, io);
+  if (gw) {
+    MOG_CHECK_ARG(ghid && ghid[0] && ghid[1]);
+    io.hid_gm = ghid[0]; io.hid_gv = ghid[1];
+    for (int i = 0; i < 8; ++i) {
+      MOG_CHECK_ARG(gw[i]);
+      io.gw[i] = gw[i];
+    }
+    asr_gen_step_kernel<true><<<mog_cdiv(G, 4), 256, 0, mog_stream(stream)>>>(c, io);
+  } else {
+    asr_gen_step_kernel<false><<<mog_cdiv(G, 4), 256, 0, mog_stream(stream)>>>(c, io);
+  }
   MOG_LAUNCH_RET();
+}
+
+extern "C" int mog_asr_gen_step(int G, int Z, int step, int fix_steps, float thr,
+                                float temperature, float scale_prior_mean, float scale_prior_var,
+                                float s, float vae_prior_mean, float vae_prior_logvar,
+                                const float* const* w, const float* const* hid,
+                                const float* eps_shift, const float* eps_scale,
+                                const float* eps_z, const float* u, float* stop, int* digits,
+                                int* live, float* ss, float* z, float* theta_back, float* zval,
+                                float* zmask, void* stream) {
+  return asr_gen_step(G, Z, step, fix_steps, thr, temperature, scale_prior_mean, scale_prior_var,
+                      s, vae_prior_mean, vae_prior_logvar, w, hid, nullptr, nullptr, eps_shift,
+                      eps_scale, eps_z, u, stop, digits, live, ss, z, theta_back, zval, zmask,
+                      stream);
+}
+
+extern "C" int mog_asr_gen_step_learned(int G, int Z, int step, int fix_steps, float thr,
+                                        float temperature, float s, float vae_prior_mean,
+                                        float vae_prior_logvar, const float* const* w,
+                                        const float* const* hid, const float* const* gw,
+                                        const float* const* ghid, const float* eps_shift,
+                                        const float* eps_scale, const float* eps_z,
+                                        const float* u, float* stop, int* digits, int* live,
+                                        float* ss, float* z, float* theta_back, float* zval,
+                                        float* zmask, void* stream) {
+  MOG_CHECK_ARG(gw && ghid);
+  return asr_gen_step(G, Z, step, fix_steps, thr, temperature, 0.0f, 1.0f, s, vae_prior_mean,
+                      vae_prior_logvar, w, hid, gw, ghid, eps_shift, eps_scale, eps_z, u, stop,
+                      digits, live, ss, z, theta_back, zval, zmask, stream);
 }
 
 extern "C" int mog_bernoulli_threshold(const float* x, const float* u, float* out, long n,

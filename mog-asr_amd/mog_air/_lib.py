@@ -89,10 +89,15 @@ _SIGS = {
     "mog_asr_unpack_parts": [I, I, I, I, P, P, I, L, P, P, P, P, I, P],
     "mog_asr_step_forward": [I, I, I, I, F, F, F, F, F, F, P, P, P, P, P, P, P, P, P, P, P, P,
                              P, P, P, P, P, P, P],
+    "mog_asr_step_forward_learned": [I, I, I, I, F, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P,
+                                     P, P, P, P, P, P, P],
     "mog_asr_terms": [I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
     "mog_asr_finalize": [I, I, I, I, P, P, F, P, P, P, P, P, P, P, P],
     "mog_asr_terms_backward": [I, I, I, I, P, P, F, F, P, P, P, P, P],
     "mog_asr_step_backward": [I, I, I, F, F, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P],
+    "mog_asr_step_backward_learned": [I, I, I, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
+    "mog_asr_gen_step_learned": [I, I, I, I, F, F, F, F, F, P, P, P, P, P, P, P, P, P, P, P, P,
+                                 P, P, P, P, P],
     "mog_asr_gen_step": [I, I, I, I, F, F, F, F, F, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P,
                          P, P],
     "mog_bernoulli_threshold": [P, P, P, L, P],

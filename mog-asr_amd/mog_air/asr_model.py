@@ -7,20 +7,31 @@ AIR model (STN read, glimpse VAE — fused bf16 step kernel or fp32 GEMMs —,
 STN write, reconstruction loss).
 
 Reference surface kept (air_number_bbox_location.py:15-56, train_air_pr.py:
-160-213): the constructor keyword arguments (cnn=True and
-fix_scale_distribution=False are rejected: the entry point uses neither), the
-train / test pair sharing one scope via ``reuse``, the loss of :1078-1079
-with every regulariser, and the result attributes (``loss, accuracy,
-mse_loss, rec_num_digits, rec_scales, rec_shifts, rec_st_back, rec_windows,
-rec_latents, z_pres_probs, reconstruction, log_variables``).
+160-213): the constructor keyword arguments (cnn=True is rejected: the entry
+point does not use it), the train / test pair sharing one scope via
+``reuse``, the loss of :1078-1079 with every regulariser, and the result
+attributes (``loss, accuracy, mse_loss, rec_num_digits, rec_scales,
+rec_shifts, rec_st_back, rec_windows, rec_latents, z_pres_probs,
+reconstruction, log_variables``).
 
 Loop: max_steps iterations on the device, the data-dependent predicate
 (:386-390) folded into a live flag per step; losses, counts and gradients
 equal the early exit.  The KL records are summed per type over the executed
 steps at the end, as the reference's TensorArrays are (:917-923).
 
+Scale prior: the constant N(-1, 0.05) with ``fix_scale_distribution=True``
+(:70-72); with False the ``gen_scale`` heads on concat([hg_t, shift_latent])
+(:482-509) give a Gaussian per image and step, and the scale KL (:729-746) is
+taken against it (the learned variants of the step kernels: two more hidden
+layers finished in the kernel, record slots gcm / gclv, douts columns 12 /
+13).  The prior enters only that KL: every other forward output has the bits
+of the fixed prior.
+
 Generation (:1124-1361): ``generate()`` runs the generative LSTMCell as the
-prior over positions and counts (asr_gen.hip), the same fixed-T schedule.
+prior over positions and counts (asr_gen.hip), the same fixed-T schedule;
+with the learned scale prior the scale latent is drawn from the gen_scale
+heads on the generated shift latent (:1170-1201) and feeds the next step's
+LSTM input.
 """
 from __future__ import annotations
 
@@ -38,18 +49,21 @@ _ops = ops._ops  # torch.ops.mog_air (csrc/torch_ops.cpp)
 # asr_cell.hip record slots
 Q = {n: i for i, n in enumerate(
     ("sm0 sm1 slv0 slv1 sl0 sl1 cm clv cl s tx ty gsm0 gsm1 gslv0 gslv1 plo lo y z act_old act "
-     "live zkl skl shkl prn zprob").split())}
-NQ = 28
-D_N = 12
+     "live zkl skl shkl prn zprob gcm gclv").split())}
+NQ = 30   # (gcm / gclv: written with the learned scale prior only)
+D_N = 12  # douts columns; D_NL with the learned scale prior (+ d gcm, d gclv)
+D_NL = 14
 LU = 312  # packed LSTM-input row: z (50) | latents (3) | h (256) | pad (3)
 
 ROOT = "air/air_model/"
 
 
-def asr_param_specs(C2, H, W2, R, G, Z, HS, HZ):
+def asr_param_specs(C2, H, W2, R, G, Z, HS, HZ, learned_scale_prior=False):
     """(TF variable name, shape): inference / generative LSTMCell kernels on
     the concatenated inputs, tf.layers.dense heads numbered in creation order
-    within their scopes (:414-474, :590-609), the glimpse VAE (vae.py)."""
+    within their scopes (:414-474, :590-609), the glimpse VAE (vae.py); with
+    ``learned_scale_prior`` the gen_scale heads (:482-509) at the end, so every
+    other variable keeps its offset and seeded draw in both modes."""
     p = ROOT
     specs = [(p + "infer_rnn_running/kernel", (C2 + Z + 3 + H, 4 * H)),
              (p + "infer_rnn_running/bias", (4 * H,)),
@@ -78,6 +92,8 @@ def asr_param_specs(C2, H, W2, R, G, Z, HS, HZ):
               (v + "generative_1/weights", (Z, G1)), (v + "generative_1/biases", (G1,)),
               (v + "generative_2/weights", (G1, G2)), (v + "generative_2/biases", (G2,)),
               (v + "gen_mean/weights", (G2, W2)), (v + "gen_mean/biases", (W2,))]
+    if learned_scale_prior:
+        specs += four("gen_scale", H + 2, 1, 2)
     return specs
 
 
@@ -89,7 +105,7 @@ class _AsrWorkspace(_Workspace):
         e = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
         self.U, self.Ug = e(T, B, LU), e(T, B, LU)
         self.Gg, self.cg, self.hg = e(T, B, 4 * H), e(T, B, H), e(T, B, H)
-        self.hid8 = e(8, T, B, 64)
+        self.hid8 = e(m._nhid, T, B, 64)
         self.arec = e(T, NQ, B)
         self.ss = e(T, B, 3)
         self.zc = e(T, B)
@@ -112,8 +128,8 @@ class _AsrWorkspace(_Workspace):
         T, H = m.max_steps, m.rnn_units
         e = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
         self.dreg = e(T, 4, B)
-        self.douts = e(T, B, D_N)
-        self.dpre = e(8, T, B, 64)
+        self.douts = e(T, B, m._dn)
+        self.dpre = e(m._nhid, T, B, 64)
         self.dhg = e(T, B, H)
         self.dcg = e(2, B, H)
         self.dGg = e(T, B, 4 * H)
@@ -149,9 +165,6 @@ class AIRModel(ModelBase):
         if cnn:
             raise NotImplementedError("cnn=True is outside the hot-path scope (train_air_pr.py "
                                       "uses cnn=False)")
-        if not fix_scale_distribution:
-            raise NotImplementedError("fix_scale_distribution=False (learned scale prior) is not "
-                                      "used by train_air_pr.py")
         if not (scale_hidden_units == shift_hidden_units == z_pres_hidden_units == 64):
             raise NotImplementedError("the ASR heads are compiled for 64 hidden units")
         if rnn_units + vae_latent_dimensions + 3 > LU:
@@ -161,7 +174,12 @@ class AIRModel(ModelBase):
         cons = list(constrains_num) if constrains_num is not None else [max_steps]
         if not 1 <= len(cons) <= 8:
             raise ValueError("1..8 allowed object counts")
-        # the scale prior is fixed (:70-72); the shift prior is generation's only
+        # the scale prior is fixed (:70-72) or the gen_scale heads'; the shift
+        # prior is generation's only
+        # (before the base constructor: the workspace reads them)
+        self.fix_scale_distribution = bool(fix_scale_distribution)
+        self._nhid = 8 if self.fix_scale_distribution else 10
+        self._dn = D_N if self.fix_scale_distribution else D_NL
         super().__init__(
             input_images=input_images, target_num_digits=target_num_digits, max_steps=max_steps,
             max_digits=max_digits, rnn_units=rnn_units, canvas_size=canvas_size,
@@ -177,7 +195,6 @@ class AIRModel(ModelBase):
             train=train, scope=scope, annealing_schedules=annealing_schedules,
             generation_batch_size=generation_batch_size, device=device, noise_seed=noise_seed,
             grad_world=grad_world, precision=precision, fused_step=fused_step)
-        self.fix_scale_distribution = True
         self.fix_steps = fix_steps
         self._fix = -1 if fix_steps is None else int(fix_steps)  # (the kernels' form)
         self.constrains_num = cons
@@ -195,7 +212,8 @@ class AIRModel(ModelBase):
         kpad = (LU - (self.vae_latent_dimensions + 3 + self.rnn_units)) * 4 * self.rnn_units
         self._bind_params("asr:" + scope, asr_param_specs(
             self.C2, self.rnn_units, self.W2, self.vae_recognition_units,
-            self.vae_generative_units, self.vae_latent_dimensions, 64, 64), reuse, seed,
+            self.vae_generative_units, self.vae_latent_dimensions, 64, 64,
+            not self.fix_scale_distribution), reuse, seed,
             pad={ROOT + "infer_rnn_running/kernel": kpad, ROOT + "gen_rnn_running/kernel": kpad})
 
     # zsum_hook / live_hook: data-parallel collectives (parallel.attach)
@@ -225,6 +243,13 @@ class AIRModel(ModelBase):
         for n in self._OUT_W:
             ts += [self._P(n + "/kernel"), self._P(n + "/bias")]
         return ts
+
+    _GEN_SCALE_W = ("gen_scale/dense", "gen_scale/dense_1", "gen_scale/dense_2",
+                    "gen_scale/dense_3")
+
+    def _gw8(self):
+        """The learned scale prior's eight tensors in the kernels' order."""
+        return [self._P(n + s) for n in self._GEN_SCALE_W for s in ("/kernel", "/bias")]
 
     def _gammas(self):
         return [float(v) for v in (
@@ -296,6 +321,12 @@ class AIRModel(ModelBase):
         gen_w = [self._P(n + "/kernel") for n in ("gen_shift/dense", "gen_shift/dense_2")]
         gen_b = [self._P(n + "/bias") for n in ("gen_shift/dense", "gen_shift/dense_2")]
         sc_w = [self._P("inf_scale/dense/kernel")[:H], self._P("inf_scale/dense_2/kernel")[:H]]
+        learned = not self.fix_scale_distribution
+        nh = self._nhid
+        if learned:
+            # the gen_scale hidden layers' chains over hg_t join the same launch
+            sc_w += [self._P("gen_scale/dense/kernel")[:H], self._P("gen_scale/dense_2/kernel")[:H]]
+            gw8 = self._gw8()
         defer = self.precision == "fp32" and self.DEFER_DECODER
         for t in range(T):
             prev = t > 0
@@ -315,7 +346,7 @@ class AIRModel(ModelBase):
             _ops.lstm_cell_forward2_(ws.G[t], ws.c[t - 1] if prev else None, ws.c[t], ws.h[t],
                                      ws.Gg[t], ws.cg[t - 1] if prev else None, ws.cg[t],
                                      ws.hg[t], B, H)
-            hid = [ws.hid8[k, t] for k in range(8)]
+            hid = [ws.hid8[k, t] for k in range(nh)]
             # (the inference and generative ReLU heads in one batched launch, with
             # the learned prior from the previous generative output (:596-602):
             # hg_{t-1}, the rows asr_pack_ copied into Ug[t])
@@ -326,15 +357,23 @@ class AIRModel(ModelBase):
                 rw.append(self._P("z_pres/prior/dense/kernel"))
                 rb.append(self._P("z_pres/prior/dense/bias"))
             gemm(ra, rw, hid[0:len(ra)], B, 64, H, H, 64, 64, epi=EPI_RELU, bias=rb)
-            gemm([ws.h[t]] * 2, sc_w, hid[6:8], B, 64, H, H, 64, 64, epi=EPI_STORE)
+            gemm([ws.h[t]] * 2 + [ws.hg[t]] * (nh - 8), sc_w, hid[6:nh], B, 64, H, H, 64, 64,
+                 epi=EPI_STORE)
             hid_l = [x if (k != 5 or fix < 0) else None for k, x in enumerate(hid)]
-            _ops.asr_step_forward_(B, t, self.train, fix, thr, temp, float(self.scale_prior_mean),
-                                   float(self.scale_prior_variance), self.scale_prior_log_variance,
-                                   float(self.hyper("constrains_num_gamma")), w20, hid_l,
-                                   ws.eps_shift[t], ws.eps_scale[t], ws.u[t], ws.stop, ws.digits,
-                                   ws.live, ws.arec[t], ws.th_f[t], ws.th_b[t], ws.ss[t],
-                                   ws.scale[t], ws.shift[t], ws.zprob[t], ws.zmask[t], ws.zval[t],
-                                   ws.zc[t])
+            outs = (ws.eps_shift[t], ws.eps_scale[t], ws.u[t], ws.stop, ws.digits, ws.live,
+                    ws.arec[t], ws.th_f[t], ws.th_b[t], ws.ss[t], ws.scale[t], ws.shift[t],
+                    ws.zprob[t], ws.zmask[t], ws.zval[t], ws.zc[t])
+            if learned:
+                _ops.asr_step_forward_learned_(B, t, self.train, fix, thr, temp,
+                                               float(self.hyper("constrains_num_gamma")), w20,
+                                               gw8, hid_l, *outs)
+            else:
+                _ops.asr_step_forward_(B, t, self.train, fix, thr, temp,
+                                       float(self.scale_prior_mean),
+                                       float(self.scale_prior_variance),
+                                       self.scale_prior_log_variance,
+                                       float(self.hyper("constrains_num_gamma")), w20, hid_l,
+                                       *outs)
             if self.live_hook is not None:
                 self.live_hook(ws.live, t)
             if self.fused_step:
@@ -409,6 +448,13 @@ class AIRModel(ModelBase):
                                                      "z_pres/log_odds/dense", "inf_scale/dense",
                                                      "inf_scale/dense_2")]
         gen_w = [self._P(n + "/kernel") for n in ("gen_shift/dense", "gen_shift/dense_2")]
+        learned = not self.fix_scale_distribution
+        nh = self._nhid
+        gen_k = (3, 4, 8, 9) if learned else (3, 4)
+        if learned:
+            # the gen_scale hidden layers read hg_t too: the same chain into dhg[t]
+            gen_w += [self._P("gen_scale/dense/kernel")[:H], self._P("gen_scale/dense_2/kernel")[:H]]
+            gw8 = self._gw8()
         steps_side = (self.VAE_WGRAD_PER_STEP and self.grad_reducer is None
                       and B >= self.SIDE_MIN_BATCH)
         side = self._side_stream() if steps_side else None
@@ -436,25 +482,34 @@ class AIRModel(ModelBase):
                 with torch.cuda.stream(self._fork(side)):
                     self._vae_weight_grads(ws, t)
             ops.stn_backward(X, ws.th_f[t], (W, W), ws.dg_all[t], want_dU=False, dtheta=ws.dth_f)
-            hid = [ws.hid8[k, t] for k in range(8)]
-            dpre = [ws.dpre[k, t] for k in range(8)]
-            _ops.asr_step_backward_(B, self.train, fix, float(self.hyper("z_pres_temperature")),
-                                    float(self.scale_prior_mean),
-                                    float(self.scale_prior_variance), float(gscale), w20,
-                                    [x if (k != 5 or fix < 0) else None for k, x in enumerate(hid)],
-                                    ws.arec[t], ws.eps_shift[t], ws.eps_scale[t], ws.dth_f,
-                                    ws.dth_b_all[t], ws.dot_all[t], ws.dreg[t],
-                                    ws.dss_carry if t < T - 1 else None, ws.douts[t],
-                                    [x if (k != 5 or fix < 0) else None
-                                     for k, x in enumerate(dpre)])
+            hid = [ws.hid8[k, t] for k in range(nh)]
+            dpre = [ws.dpre[k, t] for k in range(nh)]
+            tail = ([x if (k != 5 or fix < 0) else None for k, x in enumerate(hid)],
+                    ws.arec[t], ws.eps_shift[t], ws.eps_scale[t], ws.dth_f, ws.dth_b_all[t],
+                    ws.dot_all[t], ws.dreg[t], ws.dss_carry if t < T - 1 else None, ws.douts[t],
+                    [x if (k != 5 or fix < 0) else None for k, x in enumerate(dpre)])
+            if learned:
+                _ops.asr_step_backward_learned_(B, self.train, fix,
+                                                float(self.hyper("z_pres_temperature")),
+                                                float(gscale), w20, gw8, *tail)
+            else:
+                _ops.asr_step_backward_(B, self.train, fix,
+                                        float(self.hyper("z_pres_temperature")),
+                                        float(self.scale_prior_mean),
+                                        float(self.scale_prior_variance), float(gscale), w20,
+                                        *tail)
             # dh[t] += the five heads reading h_t; dhg[t] += the generative shift
             # heads; dhg[t-1] += the prior at step t (it reads hg_{t-1}): three
             # chains of one shape in one launch
             probs = [([dpre[k] for k in (0, 1, 2, 6, 7)], head_w, ws.dh[t], ws.dh[t]),
-                     ([dpre[3], dpre[4]], gen_w, ws.dhg[t], ws.dhg[t])]
+                     ([dpre[k] for k in gen_k], gen_w, ws.dhg[t], ws.dhg[t])]
             if fix < 0 and t > 0:
                 probs.append(([dpre[5]], [self._P("z_pres/prior/dense/kernel")], ws.dhg[t - 1],
                               ws.dhg[t - 1]))
+            if learned:
+                # 5 + 4 + 1 segments pass the launch's eight: dhg[t]'s chain on its own
+                ops.gemm_kseg_group(probs[1:2], B, H, 64, 64, 64, H, transB=True)
+                del probs[1]
             ops.gemm_kseg_group(probs, B, H, 64, 64, 64, H, transB=True)
             dc_in = ws.dc[(t + 1) % 2] if t < T - 1 else None
             dcg_in = ws.dcg[(t + 1) % 2] if t < T - 1 else None
@@ -574,17 +629,25 @@ class AIRModel(ModelBase):
         self._dw([v(ws.h)] * 5, [v(ws.dpre[k]) for k in (0, 1, 2, 6, 7)],
                  [G(n + "/kernel")[:H] for n in hs], K, H, 64, H, 64,
                  [G(n + "/bias") for n in hs])
-        self._dw([v(ws.hg)] * 2, [v(ws.dpre[3]), v(ws.dpre[4])],
-                 [G("gen_shift/dense/kernel"), G("gen_shift/dense_2/kernel")], K, H, 64, H, 64,
-                 [G("gen_shift/dense/bias"), G("gen_shift/dense_2/bias")])
+        learned = not self.fix_scale_distribution
+        dn = self._dn
+        # (the learned scale prior's hidden layers read hg_t as gen_shift's do)
+        gs = [("gen_shift/dense", 3), ("gen_shift/dense_2", 4)]
+        if learned:
+            gs += [("gen_scale/dense", 8), ("gen_scale/dense_2", 9)]
+        self._dw([v(ws.hg)] * len(gs), [v(ws.dpre[k]) for _, k in gs],
+                 [G(n + "/kernel")[:H] for n, _ in gs], K, H, 64, H, 64,
+                 [G(n + "/bias") for n, _ in gs])
         if fix < 0:
             self._dw(v(ws.Ug)[..., Z + 3:], v(ws.dpre[5]), G("z_pres/prior/dense/kernel"), K, H, 64,
                      LU, 64, G("z_pres/prior/dense/bias"))
         # the shift-latent rows of the scale hidden layers
-        self._dw([v(ws.ss)] * 2, [v(ws.dpre[6]), v(ws.dpre[7])],
-                 [G("inf_scale/dense/kernel")[H:], G("inf_scale/dense_2/kernel")[H:]], K, 2, 64,
-                 3, 64)
-        # output layers from douts [T, B, 12]
+        sh = [("inf_scale/dense", 6), ("inf_scale/dense_2", 7)]
+        if learned:
+            sh += [("gen_scale/dense", 8), ("gen_scale/dense_2", 9)]
+        self._dw([v(ws.ss)] * len(sh), [v(ws.dpre[k]) for _, k in sh],
+                 [G(n + "/kernel")[H:] for n, _ in sh], K, 2, 64, 3, 64)
+        # output layers from douts [T, B, 12] ([T, B, 14] with the learned scale prior)
         d = v(ws.douts)
         outs = (("inf_shift/dense_1", 0, 0, 2), ("inf_shift/dense_3", 1, 2, 2),
                 ("z_pres/log_odds/dense_1", 2, 4, 1), ("gen_shift/dense_1", 3, 5, 2),
@@ -598,14 +661,16 @@ class AIRModel(ModelBase):
         if fix < 0:
             one.append((v(ws.hid8[5]), d[..., 9:], G("z_pres/prior/dense_1/kernel"),
                         G("z_pres/prior/dense_1/bias")))
-        scl = (("inf_scale/dense_1", 6, 10), ("inf_scale/dense_3", 7, 11))
+        scl = [("inf_scale/dense_1", 6, 10), ("inf_scale/dense_3", 7, 11)]
+        if learned:
+            scl += [("gen_scale/dense_1", 8, 12), ("gen_scale/dense_3", 9, 13)]
         one += [(v(ws.hid8[hk]), d[..., col:], G(n + "/kernel")[:64], G(n + "/bias"))
                 for n, hk, col in scl]
         for grp, k in ((two, 2), (one, 1)):
             self._dw([g[0] for g in grp], [g[1] for g in grp], [g[2] for g in grp], K, 64, k,
-                     64, D_N, [g[3] for g in grp])
-        self._dw([v(ws.ss)] * 2, [d[..., col:] for _, _, col in scl],
-                 [G(n + "/kernel")[64:] for n, _, _ in scl], K, 2, 1, 3, D_N)
+                     64, dn, [g[3] for g in grp])
+        self._dw([v(ws.ss)] * len(scl), [d[..., col:] for _, _, col in scl],
+                 [G(n + "/kernel")[64:] for n, _, _ in scl], K, 2, 1, 3, dn)
 
     # ------------------------------------------------------- outputs -----
     def _records(self, name):
@@ -652,8 +717,9 @@ class AIRModel(ModelBase):
         (air_number_bbox_location.py:1124-1361, vae.py:51-86): up to
         ``max_steps`` objects per canvas.  Each step runs the generative
         LSTMCell on [z_prev, latents_prev], draws the shift latent from the
-        gen_shift heads, the scale latent from the fixed scale prior and z
-        from the VAE prior, decodes and binarises the window
+        gen_shift heads, the scale latent from the scale prior (the constant
+        one, or the gen_scale heads on [output, shift latent] with
+        ``fix_scale_distribution=False``) and z from the VAE prior, decodes and binarises the window
         (``sample_from_mean``), and writes it where the rounded z_pres sample
         (fixed +-100 prior with ``fix_steps``, else the learned prior on the
         previous generative output) keeps the image counting.  The write
@@ -715,6 +781,11 @@ class AIRModel(ModelBase):
         vb = {n: self._P("vae/" + n + "/biases") for n in vw}
         thr, temp = self.hyper("stopping_threshold"), self.hyper("z_pres_temperature")
         lik_std = float(self.hyper("vae_likelihood_std"))
+        learned = not self.fix_scale_distribution
+        if learned:
+            ghid = e(2, G, 64)
+            gw8 = self._gw8()
+            gsc_w = [gw8[0][:H], gw8[4][:H]]
         for t in range(T):
             cur, prv = t % 2, (t - 1) % 2
             prev = t > 0
@@ -728,12 +799,21 @@ class AIRModel(ModelBase):
             ra = [hg[cur]] * 2 + ([hg[prv] if prev else hg_zero] if fix < 0 else [])
             gemm(ra, relu_w, [hid[k] for k in range(len(ra))], G, 64, H, H, 64, 64, epi=EPI_RELU,
                  bias=relu_b)
-            _ops.asr_gen_step_(G, Z, t, fix, thr, temp, float(self.scale_prior_mean),
-                               float(self.scale_prior_variance), s, float(self.vae_prior_mean),
-                               self.vae_prior_log_variance, w6,
-                               [hid[0], hid[1], hid[2] if fix < 0 else None], eps["eps_shift"][t],
-                               eps["eps_scale"][t], eps["eps_z"][t], eps["u"][t], stop, digits,
-                               live, ss[cur], z[cur], st_back[t], zval, zmask)
+            hid3 = [hid[0], hid[1], hid[2] if fix < 0 else None]
+            tail = (eps["eps_shift"][t], eps["eps_scale"][t], eps["eps_z"][t], eps["u"][t], stop,
+                    digits, live, ss[cur], z[cur], st_back[t], zval, zmask)
+            if learned:
+                # the gen_scale hidden layers' chains over the new output (the
+                # kernel adds the shift latent's terms, bias and relu)
+                gemm([hg[cur]] * 2, gsc_w, [ghid[0], ghid[1]], G, 64, H, H, 64, 64, epi=EPI_STORE)
+                _ops.asr_gen_step_learned_(G, Z, t, fix, thr, temp, s, float(self.vae_prior_mean),
+                                           self.vae_prior_log_variance, w6, hid3, gw8,
+                                           [ghid[0], ghid[1]], *tail)
+            else:
+                _ops.asr_gen_step_(G, Z, t, fix, thr, temp, float(self.scale_prior_mean),
+                                   float(self.scale_prior_variance), s,
+                                   float(self.vae_prior_mean), self.vae_prior_log_variance, w6,
+                                   hid3, *tail)
             gemm([z[cur]], [vw["generative_1"]], [d1], G, G1, Z, Z, G1, G1, epi=EPI_SOFTPLUS,
                  bias=[vb["generative_1"]])
             gemm([d1], [vw["generative_2"]], [d2], G, G2, G1, G1, G2, G2, epi=EPI_SOFTPLUS,

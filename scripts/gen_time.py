@@ -42,10 +42,15 @@ def main():
               generation_batch_size=G)
     out = {"G": G, "max_steps": T, "calls": CALLS, "warmup": WARMUP,
            "air_generate": timed(lambda: air.generate(T))}
-    for name, fix in (("asr_generate_learned_prior", None), ("asr_generate_fix_steps_3", 3)):
+    # (*_scale_prior: fix_scale_distribution=False, the scale latent from the gen_scale heads)
+    for name, fix, fix_scale in (("asr_generate_learned_prior", None, True),
+                                 ("asr_generate_fix_steps_3", 3, True),
+                                 ("asr_generate_learned_prior_scale_prior", None, False),
+                                 ("asr_generate_fix_steps_3_scale_prior", 3, False)):
         asr = Asr(max_steps=T, cnn=False, train=False, scope="gentime_" + name, device=dev,
                   stopping_threshold=0.9, z_pres_temperature=0.1, vae_likelihood_std=0.0,
-                  constrains_area_minmax=(17, 23), fix_steps=fix, generation_batch_size=G)
+                  constrains_area_minmax=(17, 23), fix_steps=fix, generation_batch_size=G,
+                  fix_scale_distribution=fix_scale)
         out[name] = timed(asr.generate)
         out[name]["executed_steps"] = int(asr.generated_st_back.shape[1])
     print(json.dumps(out), flush=True)

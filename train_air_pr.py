@@ -1,13 +1,15 @@
 """Drop-in for the reference's AIR-ASR training entry point (train_air_pr.py):
 same command line (-r -k -gpu -data -gl -gn -gne -gm -gb -gs -ga -zt -o -t -dn
--dl -ds), dataset paths, results folder, model configuration and log lines,
+-dl -ds; --learned_scale_prior for the switch the reference keeps as a source
+line, train_air_pr.py:163-167 ``fix_scale``), dataset paths, results folder, model configuration and log lines,
 running the ASR model (mog_air.asr_model.AIRModel, the reference's
 air/air_number_bbox_location.py) on MI355X.
 
     python train_air_pr.py -dn 13 -ds 20k -gm 100 -gne 10 [--iterations N]
 
 Model configuration: train_air_pr.py:160-213 (max_steps 6, LSTM 256, VAE
-784-512-256-50 with likelihood std 0, fixed scale prior, threshold 0.9,
+784-512-256-50 with likelihood std 0, fixed scale prior (learned with
+--learned_scale_prior), threshold 0.9,
 temperature -zt, lr 1e-4, clip 1.0, number / bbox / size / area
 regularisers from the -g* flags, fix_steps when -dn names one count).
 """
@@ -35,6 +37,9 @@ def main(argv=None):
     parser.add_argument("-gs", "-gamma_size", "--gamma_size", type=float, default=0.0)
     parser.add_argument("-ga", "-gamma_area", "--gamma_area", type=float, default=0.0)
     parser.add_argument("-zt", "-z_pres_tempture", "--z_pres_tempture", type=float, default=0.1)
+    # the reference's ``fix_scale = True`` (:163-167; False commented out for the
+    # bbox / shared-size data sets): the scale prior from the gen_scale heads
+    parser.add_argument("--learned_scale_prior", action="store_true")
     args = parser.parse_args(argv)
     trainer.select_gpu(args.gpu)
 
@@ -67,7 +72,7 @@ def main(argv=None):
             None, None, max_steps=MAX_STEPS, max_digits=MAX_STEPS, rnn_units=256,
             canvas_size=canvas, windows_size=28, vae_latent_dimensions=50,
             vae_recognition_units=(512, 256), vae_generative_units=(256, 512),
-            fix_scale_distribution=True, vae_prior_mean=0.0, vae_prior_variance=1.0,
+            fix_scale_distribution=not args.learned_scale_prior, vae_prior_mean=0.0, vae_prior_variance=1.0,
             vae_likelihood_std=0.0, scale_hidden_units=64, shift_hidden_units=64,
             z_pres_hidden_units=64, z_pres_prior_log_odds=-0.01,
             z_pres_temperature=args.z_pres_tempture, stopping_threshold=0.9,
