@@ -33,6 +33,7 @@ from .model_base import R_NREC, ModelBase, _Workspace, annealed_value  # noqa: F
 from .ops import EPI_RELU, gemm
 from .params import param_specs
 from .results import Generation
+from .wgrads import TALL_X3, WgradProblem
 
 _ops = ops._ops  # torch.ops.mog_air (csrc/torch_ops.cpp)
 
@@ -440,32 +441,26 @@ class AIRModel(ModelBase, Generation):
         heads = list(enumerate(self._HEADS))
         dhid = ws.dhid.view(TB, 5, HS)
         g = self._G
-        if (self._wgroup is None and TB >= self.WGRAD_TN_MIN_ROWS
-                and H % 2 == 0 and HS % 2 == 0 and HS < 128):
+        cols = [2 if h.startswith("shift") else 1 for _, h in heads]
+        hidden = [WgradProblem(ws.h, dhid[:, zi], g(h + "/hidden/weights"),
+                               g(h + "/hidden/biases"), H, HS, H, 5 * HS) for zi, h in heads]
+        # open item: an open small-batch group wins over
+        # the tall-K kernel here (group_first), not for the VAE / recurrent rows
+        plan = self._wgrads(hidden, TB, "heads_wgrad_x3", tall=HS < 128, group_first=True)
+        if plan[0].form == TALL_X3:  # (a tall plan is one launch of every problem)
             # deterministic from the split-K batch sizes on: the five hidden
             # layers on the grouped x3 kernel (splits added in order), the 1- /
             # 2-column output layers by chunk partials added in chunk order
             # (mog_heads_output_wgrad)
-            flops = 2.0 * TB * H * HS * 5
-            with self._timed("heads_wgrad_x3", ("mfma", flops, "fp32", "x3")):
-                ops.wgrad_tn_x3([ws.h] * 5, [dhid[:, zi] for zi, _ in heads],
-                                [g(h + "/hidden/weights") for _, h in heads],
-                                [g(h + "/hidden/biases") for _, h in heads],
-                                [(H, HS, H, 5 * HS, HS)] * 5, TB, self.WGRAD_TN_X3_SPLITS)
             _ops.heads_output_wgrad_([ws.hid[zi] for zi, _ in heads],
                                      [ws.dout[zi] for zi, _ in heads],
                                      [g(h + "/output/weights") for _, h in heads],
-                                     [g(h + "/output/biases") for _, h in heads],
-                                     [2 if h.startswith("shift") else 1 for _, h in heads], TB, HS)
+                                     [g(h + "/output/biases") for _, h in heads], cols, TB, HS)
             return
-        self._dw([ws.h] * 5, [dhid[:, zi] for zi, _ in heads],
-                 [g(h + "/hidden/weights") for _, h in heads], TB, H, HS, H, 5 * HS,
-                 [g(h + "/hidden/biases") for _, h in heads])
-        for k in (1, 2):
-            sel = [(zi, h) for zi, h in heads if (2 if h.startswith("shift") else 1) == k]
-            self._dw([ws.hid[zi] for zi, _ in sel], [ws.dout[zi] for zi, _ in sel],
-                     [g(h + "/output/weights") for _, h in sel], TB, HS, k, HS, 2,
-                     [g(h + "/output/biases") for _, h in sel])
+        # the 1-column layers, then the 2-column ones: one batched launch each
+        self._wgrads([WgradProblem(ws.hid[zi], ws.dout[zi], g(h + "/output/weights"),
+                                   g(h + "/output/biases"), HS, k, HS, 2)
+                      for k in (1, 2) for zi, h in heads if cols[zi] == k], TB)
 
     def _x3p_xgrad(self, B):
         """fp32: the LSTM kernel's x-rows gradient on the pre-split
@@ -491,18 +486,12 @@ class AIRModel(ModelBase, Generation):
         over (T-1) B rows.  From WGRAD_TN_MIN_ROWS (either precision:
         fp32-level, and faster than the fp32 chain): on the bf16 matrix cores
         with exact three-piece splits (the grouped x3 kernel of the fp32 VAE
-        weight gradients, one problem, 256 x 1024 x 16,384 at B = 8192), else
-        the fp32 split-K GEMM."""
+        weight gradients, one problem, 256 x 1024 x 16,384 at B = 8192:
+        deterministic), else the fp32 split-K GEMM."""
         B, T, H, C2 = ws.B, self.max_steps, self.rnn_units, self.C2
         gK = self._G("rnn/basic_lstm_cell/kernel")
-        K = (T - 1) * B
-        if self.REC_WGRAD_X3 and K >= self.WGRAD_TN_MIN_ROWS:
-            # the grouped x3 kernel with one problem: deterministic
-            with self._timed("rec_wgrad_x3", ("mfma", 2.0 * K * H * 4 * H, "fp32", "x3")):
-                ops.wgrad_tn_x3([ws.h], [ws.dG[1:]], [gK[C2:]], [None],
-                                [(H, 4 * H, H, 4 * H, 4 * H)], K, self.WGRAD_TN_X3_SPLITS)
-        else:
-            self._dw(ws.h, ws.dG[1:], gK[C2:], K, H, 4 * H, H, 4 * H)
+        self._wgrads([WgradProblem(ws.h, ws.dG[1:], gK[C2:], None, H, 4 * H, H, 4 * H)],
+                     (T - 1) * B, "rec_wgrad_x3", tall=self.REC_WGRAD_X3, check_even=False)
 
     def _weight_grads_lstm(self, X, ws, side=False, rec_done=False):
         """LSTM kernel / bias gradients.  Data parallel: the x-part X^T dGsum

@@ -43,6 +43,7 @@ from . import ops
 from .model_base import ModelBase, _Workspace
 from .ops import EPI_RELU, EPI_SIGMOID_NOISE, EPI_SOFTPLUS, EPI_STORE, gemm
 from .vae import _step_rows
+from .wgrads import WgradProblem
 
 _ops = ops._ops  # torch.ops.mog_air (csrc/torch_ops.cpp)
 
@@ -556,17 +557,12 @@ class AIRModel(ModelBase):
         v = _step_rows(T, t)
         gKi = self._Kpad("infer_rnn_running/kernel", "grad")
         gKg = self._Kpad("gen_rnn_running/kernel", "grad")
-        if self.REC_WGRAD_X3 and K >= self.WGRAD_TN_MIN_ROWS:
-            # both cells in one grouped x3 launch (as AIR's recurrent rows,
-            # AIRModel._dw_rec): 312 x 1024 x K each, deterministic
-            with self._timed("rec_wgrad_x3", ("mfma", 2 * 2.0 * K * LU * 4 * H, "fp32", "x3")):
-                ops.wgrad_tn_x3([v(ws.U), v(ws.Ug)], [v(ws.dG), v(ws.dGg)],
-                                [gKi[self.C2:], gKg], [None, self._G("gen_rnn_running/bias")],
-                                [(LU, 4 * H, LU, 4 * H, 4 * H)] * 2, K, self.WGRAD_TN_X3_SPLITS)
-            return
-        self._dw(v(ws.U), v(ws.dG), gKi[self.C2:], K, LU, 4 * H, LU, 4 * H)
-        self._dw(v(ws.Ug), v(ws.dGg), gKg, K, LU, 4 * H, LU, 4 * H,
-                 self._G("gen_rnn_running/bias"))
+        # tall (plan_wgrads): both cells in one grouped x3 launch, as AIR's
+        # recurrent rows: 312 x 1024 x K each, deterministic
+        self._wgrads([WgradProblem(v(ws.U), v(ws.dG), gKi[self.C2:], None, LU, 4 * H, LU, 4 * H),
+                      WgradProblem(v(ws.Ug), v(ws.dGg), gKg, self._G("gen_rnn_running/bias"),
+                                   LU, 4 * H, LU, 4 * H)],
+                     K, "rec_wgrad_x3", tall=self.REC_WGRAD_X3, check_even=False)
 
     # (with VAE_WGRAD_PER_STEP) the recurrent-rows gradients per step too (9.20 ->
     # 8.96 ms; the heads' gradients per step as well measured neutral, 9.01 vs
@@ -622,55 +618,44 @@ class AIRModel(ModelBase):
         K = B if t is not None else B * T
         v = _step_rows(T, t)
         G = self._G
-        fix = self._fix
-        # hidden layers reading h_t, hg_t, hg_{t-1}
-        hs = ("inf_shift/dense", "inf_shift/dense_2", "z_pres/log_odds/dense", "inf_scale/dense",
-              "inf_scale/dense_2")
-        self._dw([v(ws.h)] * 5, [v(ws.dpre[k]) for k in (0, 1, 2, 6, 7)],
-                 [G(n + "/kernel")[:H] for n in hs], K, H, 64, H, 64,
-                 [G(n + "/bias") for n in hs])
-        learned = not self.fix_scale_distribution
-        dn = self._dn
-        # (the learned scale prior's hidden layers read hg_t as gen_shift's do)
-        gs = [("gen_shift/dense", 3), ("gen_shift/dense_2", 4)]
-        if learned:
-            gs += [("gen_scale/dense", 8), ("gen_scale/dense_2", 9)]
-        self._dw([v(ws.hg)] * len(gs), [v(ws.dpre[k]) for _, k in gs],
-                 [G(n + "/kernel")[:H] for n, _ in gs], K, H, 64, H, 64,
-                 [G(n + "/bias") for n, _ in gs])
-        if fix < 0:
-            self._dw(v(ws.Ug)[..., Z + 3:], v(ws.dpre[5]), G("z_pres/prior/dense/kernel"), K, H, 64,
-                     LU, 64, G("z_pres/prior/dense/bias"))
+        P = WgradProblem
+
+        def hidden(X, lda, layers):
+            """[H x 64] hidden layers reading X, one batched launch: (layer, its dpre)"""
+            self._wgrads([P(X, v(ws.dpre[k]), G(n + "/kernel")[:H], G(n + "/bias"), H, 64, lda, 64)
+                          for n, k in layers], K)
+        # (the learned scale prior's layers sit beside gen_shift's and inf_scale's)
+        gen_scale = [] if self.fix_scale_distribution else [("gen_scale/dense", 8),
+                                                            ("gen_scale/dense_2", 9)]
+        inf_scale = [("inf_scale/dense", 6), ("inf_scale/dense_2", 7)]
+        hidden(v(ws.h), H, [("inf_shift/dense", 0), ("inf_shift/dense_2", 1),
+                            ("z_pres/log_odds/dense", 2)] + inf_scale)
+        hidden(v(ws.hg), H, [("gen_shift/dense", 3), ("gen_shift/dense_2", 4)] + gen_scale)
+        if self._fix < 0:  # (the prior reads hg_{t-1}, inside Ug)
+            hidden(v(ws.Ug)[..., Z + 3:], LU, [("z_pres/prior/dense", 5)])
         # the shift-latent rows of the scale hidden layers
-        sh = [("inf_scale/dense", 6), ("inf_scale/dense_2", 7)]
-        if learned:
-            sh += [("gen_scale/dense", 8), ("gen_scale/dense_2", 9)]
-        self._dw([v(ws.ss)] * len(sh), [v(ws.dpre[k]) for _, k in sh],
-                 [G(n + "/kernel")[H:] for n, _ in sh], K, 2, 64, 3, 64)
-        # output layers from douts [T, B, 12] ([T, B, 14] with the learned scale prior)
-        d = v(ws.douts)
-        outs = (("inf_shift/dense_1", 0, 0, 2), ("inf_shift/dense_3", 1, 2, 2),
-                ("z_pres/log_odds/dense_1", 2, 4, 1), ("gen_shift/dense_1", 3, 5, 2),
-                ("gen_shift/dense_3", 4, 7, 2))
-        # grouped by shape, one batched launch per group (each is a tiny
-        # [64 x 1..2] product over K = T*B rows: launch-bound one by one)
-        one = [(v(ws.hid8[hk]), d[..., col:], G(n + "/kernel"), G(n + "/bias"))
-               for n, hk, col, k in outs if k == 1]
-        two = [(v(ws.hid8[hk]), d[..., col:], G(n + "/kernel"), G(n + "/bias"))
-               for n, hk, col, k in outs if k == 2]
-        if fix < 0:
-            one.append((v(ws.hid8[5]), d[..., 9:], G("z_pres/prior/dense_1/kernel"),
-                        G("z_pres/prior/dense_1/bias")))
+        self._wgrads([P(v(ws.ss), v(ws.dpre[k]), G(n + "/kernel")[H:], None, 2, 64, 3, 64)
+                      for n, k in inf_scale + gen_scale], K)
+        # output layers from douts [T, B, 12] ([T, B, 14] with the learned
+        # scale prior): (layer, its hidden activation, its douts column)
+        d, dn = v(ws.douts), self._dn
+        two = [("inf_shift/dense_1", 0, 0), ("inf_shift/dense_3", 1, 2),
+               ("gen_shift/dense_1", 3, 5), ("gen_shift/dense_3", 4, 7)]
+        one = [("z_pres/log_odds/dense_1", 2, 4)] + (
+            [("z_pres/prior/dense_1", 5, 9)] if self._fix < 0 else [])
         scl = [("inf_scale/dense_1", 6, 10), ("inf_scale/dense_3", 7, 11)]
-        if learned:
+        if gen_scale:
             scl += [("gen_scale/dense_1", 8, 12), ("gen_scale/dense_3", 9, 13)]
-        one += [(v(ws.hid8[hk]), d[..., col:], G(n + "/kernel")[:64], G(n + "/bias"))
-                for n, hk, col in scl]
-        for grp, k in ((two, 2), (one, 1)):
-            self._dw([g[0] for g in grp], [g[1] for g in grp], [g[2] for g in grp], K, 64, k,
-                     64, dn, [g[3] for g in grp])
-        self._dw([v(ws.ss)] * len(scl), [d[..., col:] for _, _, col in scl],
-                 [G(n + "/kernel")[64:] for n, _, _ in scl], K, 2, 1, 3, dn)
+
+        def out(n, h, c, k):
+            """a [64 x k] output layer; its kernel's first 64 rows are all of
+            it, but for scl's, which have two more for the shift latent"""
+            return P(v(ws.hid8[h]), d[..., c:], G(n + "/kernel")[:64], G(n + "/bias"), 64, k, 64, dn)
+        # one batched launch per shape (each is a tiny [64 x 1..2] product
+        # over K = T*B rows: launch-bound one by one)
+        self._wgrads([out(*l, 2) for l in two] + [out(*l, 1) for l in one + scl], K)
+        self._wgrads([P(v(ws.ss), d[..., col:], G(n + "/kernel")[64:], None, 2, 1, 3, dn)
+                      for n, _, col in scl], K)
 
     # ------------------------------------------------------- outputs -----
     def _records(self, name):

@@ -425,7 +425,7 @@ class ModelBase(GlimpseVAE, WeightGradients, GraphCapture, Results):
     # ---------------------------------------------------------- backward ---
     def _backward_body_grouped(self, X, ws) -> None:
         """_backward_body; small batch, one GPU: the fp32-chain weight
-        gradients it meets are collected (_dw) and run as one grouped launch
+        gradients it meets are collected (_wgrads) and run as one grouped launch
         at the end."""
         self._wgroup = (self._wgroup_obj if (self.WGRAD_GROUP and ws.B < self.SIDE_MIN_BATCH
                                              and self.grad_reducer is None) else None)

@@ -11,6 +11,7 @@ import torch  # noqa: E402
 
 import test_gpu_streams as ts  # noqa: E402
 from mog_air import ops  # noqa: E402
+from mog_air.wgrads import WgradProblem  # noqa: E402
 
 B = 1024
 data = ts._data(B)
@@ -49,11 +50,11 @@ def x3_tn():
 
 
 def dw_fp32():
-    m._dw(ws.z, ws.dd1, scratch, TB, Z, G1, Z, G1)
+    m._wgrads([WgradProblem(ws.z, ws.dd1, scratch, None, Z, G1, Z, G1)], TB)
 
 
 def dw_fp32_n50():
-    m._dw(ws.a2, ws.dmu, scratch, TB, R2, Z, R2, Z)
+    m._wgrads([WgradProblem(ws.a2, ws.dmu, scratch, None, R2, Z, R2, Z)], TB)
 
 
 Xb = torch.zeros((TB, 784), device="cuda:0", dtype=torch.bfloat16)
