@@ -470,6 +470,37 @@ int mog_clip_adam(float* params, float* grads, float* m, float* v, const long* o
                   int nblocks, float* sumsq, float clip, float lr_t, float beta1, float beta2,
                   float eps, void* stream);
 
+/* ---- cnn=True image encoder (air_model.py:763-810) -------------------------
+ * x [B, 2500] read as NHWC [B, 50, 50, 1] -> conv1 5x5 same (1 -> F) + bias +
+ * relu -> max-pool 2x2/2 valid -> conv2 5x5 same (F -> F) + bias + relu ->
+ * max-pool 2x2/2 valid (conv2 row / column 24 dropped) -> conv3 5x5 same
+ * (F -> F) + bias + relu -> feat [B, 144 F] (index (y 12 + x) F + f).  Kernels
+ * HWIO (w1 [5,5,1,F], w2 / w3 [5,5,F,F]).  `filters` (F) must be 8.
+ * Forward: every conv output is one fp32 fmaf chain from +0 over (ky, kx, cin)
+ * (cin fastest; padded taps multiply a zero), then + bias, then relu: bit-exact
+ * against im2col + the dense chain.  pool1 [B, 25, 25, F] and pool2
+ * [B, 12, 12, F] (16-byte aligned) are kept for the backward, which recomputes
+ * the pre-pool planes.
+ * Backward: dF [B, 144 F] -> the six gradients, STORED (not accumulated) into
+ * gw1 .. gb3; no image gradient.  Max-pool gradient to the first maximum in
+ * row-major window order; relu gradient dy (y > 0).  Deterministic: workgroup g
+ * sums images [g n, (g+1) n), n = images_per_wg (1..8), in image order into
+ * part[g], a second launch adds the workgroups in a fixed order (no atomics):
+ * the same bits on every run of one B and one n.  mog_cnn_enc_images_per_wg(B)
+ * is the n to use by default (B / 512 clamped to 1..8).  part: scratch of
+ * part_elems >= mog_cnn_enc_partial_elems(B, images_per_wg) floats. */
+int mog_cnn_enc_images_per_wg(int B);
+long mog_cnn_enc_partial_elems(int B, int images_per_wg);
+int mog_cnn_enc_forward(const float* x, const float* w1, const float* b1, const float* w2,
+                        const float* b2, const float* w3, const float* b3, int B, int filters,
+                        float* pool1, float* pool2, float* feat, void* stream);
+int mog_cnn_enc_backward(const float* x, const float* w1, const float* b1, const float* w2,
+                         const float* b2, const float* w3, const float* pool1,
+                         const float* pool2, const float* feat, const float* dF, int B,
+                         int filters, int images_per_wg, float* part, long part_elems,
+                         float* gw1, float* gb1, float* gw2, float* gb2, float* gw3, float* gb3,
+                         void* stream);
+
 /* ---- generation loop prior draws (air_model.py:1001-1146, vae.py:51-86) --
  * Per image i < G: s = sigmoid(s_pm + eps_scale[i] sqrt(exp(s_plv))),
  * (tx, ty) = tanh(h_pm + eps_shift[i][:] sqrt(exp(h_plv))), theta_back[i] =

@@ -306,6 +306,62 @@ void stn_write_parts_(const Tensor& U, int64_t N, int64_t Hin, int64_t Win, cons
   check(mog_stn_write_parts(pu, N, Hin, Win, pt, Hout, Wout, pz, pm, pp, pr, o.stream()), o.name);
 }
 
+// ----------------------------------------------- cnn=True image encoder ----
+// (mog_cnn_enc_forward / mog_cnn_enc_backward; F = w1's last dimension)
+void cnn_enc_forward_(const Tensor& x, const Tensor& w1, const Tensor& b1, const Tensor& w2,
+                      const Tensor& b2, const Tensor& w3, const Tensor& b3, int64_t B, int64_t F,
+                      Tensor pool1, Tensor pool2, Tensor feat) {
+  Op o("cnn_enc_forward_");
+  TORCH_CHECK(B >= 0 && F >= 1, o.name, ": bad shape");
+  float* pp1 = o.f(pool1, B * 625 * F, "pool1");
+  float* pp2 = o.f(pool2, B * 144 * F, "pool2");
+  float* pf = o.f(feat, B * 144 * F, "feat");
+  float* px = o.f(x, B * 2500, "x");
+  float* pw1 = o.f(w1, 25 * F, "w1");
+  float* pb1 = o.f(b1, F, "b1");
+  float* pw2 = o.f(w2, 25 * F * F, "w2");
+  float* pb2 = o.f(b2, F, "b2");
+  float* pw3 = o.f(w3, 25 * F * F, "w3");
+  float* pb3 = o.f(b3, F, "b3");
+  GUARD(o);
+  check(mog_cnn_enc_forward(px, pw1, pb1, pw2, pb2, pw3, pb3, (int)B, (int)F, pp1, pp2, pf,
+                            o.stream()),
+        o.name);
+}
+
+void cnn_enc_backward_(const Tensor& x, const Tensor& w1, const Tensor& b1, const Tensor& w2,
+                       const Tensor& b2, const Tensor& w3, const Tensor& pool1,
+                       const Tensor& pool2, const Tensor& feat, const Tensor& dF, int64_t B,
+                       int64_t F, int64_t images_per_wg, Tensor part, Tensor gw1, Tensor gb1,
+                       Tensor gw2, Tensor gb2, Tensor gw3, Tensor gb3) {
+  Op o("cnn_enc_backward_");
+  TORCH_CHECK(B >= 0 && F >= 1, o.name, ": bad shape");
+  const long pe = mog_cnn_enc_partial_elems((int)B, (int)images_per_wg);
+  TORCH_CHECK(B == 0 || pe > 0, o.name, ": images_per_wg out of range");
+  float* ppt = o.f(part, pe, "part");
+  float* pgw1 = o.f(gw1, 25 * F, "gw1");
+  float* pgb1 = o.f(gb1, F, "gb1");
+  float* pgw2 = o.f(gw2, 25 * F * F, "gw2");
+  float* pgb2 = o.f(gb2, F, "gb2");
+  float* pgw3 = o.f(gw3, 25 * F * F, "gw3");
+  float* pgb3 = o.f(gb3, F, "gb3");
+  float* px = o.f(x, B * 2500, "x");
+  float* pw1 = o.f(w1, 25 * F, "w1");
+  float* pb1 = o.f(b1, F, "b1");
+  float* pw2 = o.f(w2, 25 * F * F, "w2");
+  float* pb2 = o.f(b2, F, "b2");
+  float* pw3 = o.f(w3, 25 * F * F, "w3");
+  float* pp1 = o.f(pool1, B * 625 * F, "pool1");
+  float* pp2 = o.f(pool2, B * 144 * F, "pool2");
+  float* pf = o.f(feat, B * 144 * F, "feat");
+  float* pdf = o.f(dF, B * 144 * F, "dF");
+  GUARD(o);
+  check(mog_cnn_enc_backward(px, pw1, pb1, pw2, pb2, pw3, pp1, pp2, pf, pdf, (int)B, (int)F,
+                             (int)images_per_wg, ppt, pe, pgw1, pgb1, pgw2, pgb2, pgw3, pgb3,
+                             o.stream()),
+        o.name);
+}
+
 // ----------------------------------------------------------------- LSTM ----
 void lstm_cell_forward_(const Tensor& G, const optional<Tensor>& bias,
                         const optional<Tensor>& c_prev, Tensor c_out, Tensor h_out, int64_t B,
@@ -1529,6 +1585,15 @@ TORCH_LIBRARY_FRAGMENT(mog_air, m) {
   m.def(
       "asr_unpack_parts_(int B, int Z, int H, int ld, Tensor dU, Tensor dUg, int nparts, "
       "Tensor(a!) dz, Tensor(b!) dss, Tensor(c!) dh, Tensor(d!) dhg, int acc_dz) -> ()");
+  m.def(
+      "cnn_enc_forward_(Tensor x, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor w3, "
+      "Tensor b3, int B, int F, Tensor(a!) pool1, Tensor(b!) pool2, Tensor(c!) feat) -> ()");
+  m.def(
+      "cnn_enc_backward_(Tensor x, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor w3, "
+      "Tensor pool1, Tensor pool2, Tensor feat, Tensor dF, int B, int F, int images_per_wg, "
+      "Tensor(a!) part, "
+      "Tensor(b!) gw1, Tensor(c!) gb1, Tensor(d!) gw2, Tensor(e!) gb2, Tensor(f!) gw3, "
+      "Tensor(g!) gb3) -> ()");
   m.def("copy32_batch_(Tensor(a!)[] dst, Tensor[] src) -> ()");
   m.def("transpose32_batch_(Tensor(a!)[] dst, Tensor[] src) -> ()");
   m.def(
@@ -1688,6 +1753,8 @@ TORCH_LIBRARY_IMPL(mog_air, CUDA, m) {
   m.impl("split3_sum_bf16_", &split3_sum_bf16_);
   m.impl("lstm_cell_backward_parts_", &lstm_cell_backward_parts_);
   m.impl("asr_unpack_parts_", &asr_unpack_parts_);
+  m.impl("cnn_enc_forward_", &cnn_enc_forward_);
+  m.impl("cnn_enc_backward_", &cnn_enc_backward_);
   m.impl("copy32_batch_", &copy32_batch_);
   m.impl("transpose32_batch_", &transpose32_batch_);
   m.impl("air_step_forward_", &air_step_forward_);

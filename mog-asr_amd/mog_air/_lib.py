@@ -101,10 +101,15 @@ _SIGS = {
     "mog_asr_gen_step": [I, I, I, I, F, F, F, F, F, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P,
                          P, P],
     "mog_bernoulli_threshold": [P, P, P, L, P],
+    "mog_cnn_enc_images_per_wg": [I],
+    "mog_cnn_enc_partial_elems": [I, I],
+    "mog_cnn_enc_forward": [P] * 7 + [I, I, P, P, P, P],
+    "mog_cnn_enc_backward": [P] * 10 + [I, I, I, P, L] + [P] * 7,
 }
 
 # entry points that do not return an int status
-_RESTYPE = {"mog_wgrad_tn_work_elems": L, "mog_heads_output_wgrad_work_elems": L}
+_RESTYPE = {"mog_wgrad_tn_work_elems": L, "mog_heads_output_wgrad_work_elems": L,
+            "mog_cnn_enc_partial_elems": L}
 
 _lib = None
 

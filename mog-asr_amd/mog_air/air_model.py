@@ -19,6 +19,11 @@ runs max_steps iterations on the device with the predicate folded into a
 per-step ``live`` flag; every loss term, count and gradient is identical to
 the early exit, and the ``rec_*`` outputs are sliced to the executed steps.
 No host synchronisation happens inside a train step.
+
+``cnn=True`` (the reference default, air_model.py:763-810): the LSTM reads the
+1152 features of a three-convolution encoder (csrc/cnn_enc.hip) instead of
+the canvas; fp32, one device, ``cnn_filters=8``, 50 x 50 canvases (DESIGN.md
+§4.14).  ``rnn_input`` holds them after a forward.
 """
 from __future__ import annotations
 
@@ -31,7 +36,7 @@ import torch
 from . import ops
 from .model_base import R_NREC, ModelBase, _Workspace, annealed_value  # noqa: F401
 from .ops import EPI_RELU, gemm
-from .params import param_specs
+from .params import CNN_LAYERS, cnn_param_specs, param_specs
 from .results import Generation
 from .wgrads import TALL_X3, WgradProblem
 
@@ -85,9 +90,19 @@ class AIRModel(ModelBase, Generation):
                  grad_world: int = 1, precision: str = "fp32", fused_step: bool = True,
                  batch_vae: bool = True):
         if cnn:
-            raise NotImplementedError(
-                "cnn=True (air_model.py:763-810) is outside the hot-path scope; the entry "
-                "points use cnn=False")
+            # the reference hard-codes the 50 x 50 canvas and the 12 x 12 plane
+            # it flattens (air_model.py:763-810)
+            if canvas_size != ops.CNN_CANVAS:
+                raise ValueError(f"cnn=True reads a {ops.CNN_CANVAS} x {ops.CNN_CANVAS} canvas "
+                                 f"(air_model.py:763-810), got canvas_size={canvas_size}")
+            if cnn_filters != 8:
+                raise NotImplementedError(
+                    "cnn=True is built for cnn_filters=8 (the reference default), got "
+                    f"{cnn_filters}")
+            if precision != "fp32":
+                raise NotImplementedError(
+                    "cnn=True runs in fp32 only; the bf16 configuration of the encoder is a "
+                    "follow-up")
         if not (scale_hidden_units == shift_hidden_units == z_pres_hidden_units):
             raise NotImplementedError("heads must share one hidden width")
         super().__init__(
@@ -113,10 +128,19 @@ class AIRModel(ModelBase, Generation):
         self.num_prior = num_prior
         if num_prior is not None:
             self.marginal = marginal_objective(num_prior, self.max_steps)
-        self._bind_params(scope, param_specs(
-            self.C2, self.rnn_units, self.W2, self.vae_recognition_units,
+        # cnn=True: the LSTM reads the conv encoder's 12 x 12 x F features
+        # instead of the canvas (air_model.py:763-810); the image still feeds
+        # the STN read and the reconstruction loss
+        self.cnn, self.cnn_filters = bool(cnn), int(cnn_filters)
+        if self.cnn:
+            self.lstm_in = ops.CNN_POOL2 ** 2 * self.cnn_filters
+        specs = param_specs(
+            self.lstm_in, self.rnn_units, self.W2, self.vae_recognition_units,
             self.vae_generative_units, self.vae_latent_dimensions, scale_hidden_units,
-            z_pres_hidden_units), reuse, seed)
+            z_pres_hidden_units)
+        if self.cnn:  # appended: every other variable keeps its offset and draw
+            specs += cnn_param_specs(self.cnn_filters)
+        self._bind_params(scope, specs, reuse, seed)
 
     _HEADS = ("scale/mean", "scale/log_variance", "shift/mean", "shift/log_variance",
               "z_pres/log_odds")
@@ -124,8 +148,34 @@ class AIRModel(ModelBase, Generation):
     def _bucket_split(self) -> int:
         """Flat offset where the glimpse-side variables (heads, VAE) start:
         [0, split) is the LSTM kernel + bias, [split, total) everything else
-        (params.param_specs order)."""
+        (params.param_specs order; cnn=True appends the encoder's there)."""
         return self.params.offsets[self._SCOPE_PREFIX + "scale/mean/hidden/weights"]
+
+    # ------------------------------------------------ cnn=True encoder ---
+    def _cnn_tensors(self, buf: str = "flat"):
+        """(w1, b1, w2, b2, w3, b3) of the encoder in the parameter (or
+        gradient) buffer."""
+        return [self.params.view("air/cnn/" + layer + "/" + n, buf)
+                for layer in CNN_LAYERS for n in ("kernel", "bias")]
+
+    def _cnn_forward(self, X, ws):
+        """conv1 -> pool -> conv2 -> pool -> conv3 in one launch
+        (csrc/cnn_enc.hip); returns the features [B, 144 F], the LSTM's input."""
+        if self.grad_reducer is not None or self.live_hook is not None:
+            raise NotImplementedError(
+                "cnn=True is the single-device step; data parallelism (a grad_reducer or "
+                "live_hook attached) is a follow-up")
+        with self._timed("cnn_enc_forward"):
+            ops.cnn_enc_forward(X, self._cnn_tensors(), ws.pool1, ws.pool2, ws.feat)
+        return ws.feat
+
+    @property
+    def rnn_input(self):
+        """The LSTM input of the last forward (the reference's attribute):
+        the encoder's features [B, 144 F] (cnn=True) or the flat canvas."""
+        if self._ws is None or not self._outputs_ready:
+            raise RuntimeError("rnn_input: no forward has run")
+        return self._ws.feat if self.cnn else self._loss_inputs[0]
 
     # batched VAE: every step's heads and scalars in one launch each after
     # the LSTM chain (False: per step, as the unbatched loop;
@@ -140,13 +190,19 @@ class AIRModel(ModelBase, Generation):
         HS = self.scale_hidden_units
         K = self._P("rnn/basic_lstm_cell/kernel")
         bK = self._P("rnn/basic_lstm_cell/bias")
-        Wx, Wh = K[:C2], K[C2:]
+        NX = self.lstm_in
+        Wx, Wh = K[:NX], K[NX:]
+        # the LSTM's input: the canvas, or the encoder's features (main
+        # stream, ahead of everything that reads them)
+        Xl = self._cnn_forward(X, ws) if self.cnn else X
         side = self._side_stream() if ws.noise_side else None
         ws.noise_side = False
+        if self.cnn and need_grad and self._x3p_xgrad(B):
+            self._x_split3(Xl, ws)  # (main stream: the features are made there)
         with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
             # (after the noise on the side stream, when it went there)
             self._reset_loop_state(ws)
-            if need_grad and self._x3p_xgrad(B):
+            if need_grad and self._x3p_xgrad(B) and not self.cnn:
                 self._x_split3(X, ws)  # the x-part gradient's A operand, split once per step
             if need_grad and self.precision == "bf16":
                 self._x_bf16(X, ws)  # (likewise: the bf16 x-part gradient's A operand)
@@ -165,7 +221,7 @@ class AIRModel(ModelBase, Generation):
         batched = self._batched_vae(B)
         # hoisted x-projection of the LSTM input (input is loop-invariant in AIR)
         with self._timed("lstm_x_projection"):
-            gemm([X], [Wx], [ws.Gx], B, 4 * H, C2, C2, 4 * H, 4 * H)
+            gemm([Xl], [Wx], [ws.Gx], B, 4 * H, NX, NX, 4 * H, 4 * H)
         if side is not None:
             torch.cuda.current_stream().wait_event(pre_done)
         w1 = [self._P(h + "/hidden/weights") for h in self._HEADS]
@@ -289,7 +345,7 @@ class AIRModel(ModelBase, Generation):
         # the gradient buffer and the LSTM chain's dG sum, zeroed in one launch
         # (the fp32 x3p x-rows gradient reads every step's dG instead of the
         # sum: mog_split3_sum_bf16)
-        if self._x3p_xgrad(ws.B):
+        if self._x3p_xgrad(ws.B) and not self.cnn:
             _ops.fill32_batch_([st.grad], [0])
         else:
             _ops.fill32_batch_([st.grad, ws.dGsum], [0, 0])
@@ -297,12 +353,12 @@ class AIRModel(ModelBase, Generation):
 
     def _backward_body(self, X: torch.Tensor, ws: _Workspace) -> None:
         B, T, H = ws.B, self.max_steps, self.rnn_units
-        W, C2 = self.windows_size, self.C2
+        W = self.windows_size
         HS = self.scale_hidden_units
         TB = T * B
         K = self._P("rnn/basic_lstm_cell/kernel")
         bK = self._P("rnn/basic_lstm_cell/bias")
-        Wh = K[C2:]
+        Wx, Wh = K[:self.lstm_in], K[self.lstm_in:]
         w2 = [self._P(h + "/output/weights") for h in self._HEADS]
         gscale = self._gscale(B)
         prior_lo = self.hyper("z_pres_prior_log_odds")
@@ -387,7 +443,8 @@ class AIRModel(ModelBase, Generation):
             split = self._bucket_split()
             self._reduce_bucket(split, self.params.total)
         rec_early = T > 1 and heads_side and self.REC_WGRAD_SIDE
-        dGsum = None if self._x3p_xgrad(B) else ws.dGsum
+        # (cnn=True: the encoder's input gradient reads the sum in either form)
+        dGsum = None if self._x3p_xgrad(B) and not self.cnn else ws.dGsum
         # a small batch's dh GEMM in DH_PARTS K slices that the next cell
         # backward adds to the heads' dh in part order (_dh_parts)
         parts = self._dh_parts(B)
@@ -414,7 +471,15 @@ class AIRModel(ModelBase, Generation):
             elif t > 0:
                 gemm([ws.dG[t]], [Wh], [ws.dh[t - 1]], B, H, 4 * H, 4 * H, 4 * H, H,
                      transB=True, Cin=[ws.dh[t - 1]])
-        self._weight_grads_lstm(X, ws, side=heads_side, rec_done=rec_early)
+        self._weight_grads_lstm(ws.feat if self.cnn else X, ws, side=heads_side,
+                                rec_done=rec_early)
+        if self.cnn:
+            # dF = (sum_t dG_t) Wx^T, then the encoder's backward (main stream)
+            gemm([ws.dGsum], [Wx], [ws.dF], B, self.lstm_in, 4 * H, 4 * H, 4 * H, self.lstm_in,
+                 transB=True)
+            with self._timed("cnn_enc_backward"):
+                ops.cnn_enc_backward(X, self._cnn_tensors(), ws.pool1, ws.pool2, ws.feat, ws.dF,
+                                     ws.cnn_part, self._cnn_tensors("grad"))
         if heads_side:  # (everything on the side stream: VAE, heads, dW_rec)
             torch.cuda.current_stream().wait_stream(self._side_stream())
             torch.cuda.current_stream().wait_stream(self._stream3())
@@ -482,13 +547,13 @@ class AIRModel(ModelBase, Generation):
             self._dw_rec(ws)
 
     def _dw_rec(self, ws):
-        """The LSTM kernel's recurrent rows: gK[C2:] += sum_t h[t-1]^T dG[t]
+        """The LSTM kernel's recurrent rows: gK[lstm_in:] += sum_t h[t-1]^T dG[t]
         over (T-1) B rows.  From WGRAD_TN_MIN_ROWS (either precision:
         fp32-level, and faster than the fp32 chain): on the bf16 matrix cores
         with exact three-piece splits (the grouped x3 kernel of the fp32 VAE
         weight gradients, one problem, 256 x 1024 x 16,384 at B = 8192:
         deterministic), else the fp32 split-K GEMM."""
-        B, T, H, C2 = ws.B, self.max_steps, self.rnn_units, self.C2
+        B, T, H, C2 = ws.B, self.max_steps, self.rnn_units, self.lstm_in
         gK = self._G("rnn/basic_lstm_cell/kernel")
         self._wgrads([WgradProblem(ws.h, ws.dG[1:], gK[C2:], None, H, 4 * H, H, 4 * H)],
                      (T - 1) * B, "rec_wgrad_x3", tall=self.REC_WGRAD_X3, check_even=False)
@@ -498,8 +563,9 @@ class AIRModel(ModelBase, Generation):
         (2500 x 1024, 10 MB) is produced in row chunks, each handed to the
         all-reduce as soon as it is final, so the collective of chunk i runs
         under the GEMM of chunk i+1; the recurrent rows and the bias go last.
-        rec_done: the recurrent rows were forked already (_weight_grads_rec_side)."""
-        B, T, H, C2 = ws.B, self.max_steps, self.rnn_units, self.C2
+        rec_done: the recurrent rows were forked already (_weight_grads_rec_side).
+        X: the LSTM's input (lstm_in wide: the canvas or the encoder's features)."""
+        B, T, H, C2 = ws.B, self.max_steps, self.rnn_units, self.lstm_in
         gK = self._G("rnn/basic_lstm_cell/kernel")
         gbK = self._G("rnn/basic_lstm_cell/bias")
         if rec_done:

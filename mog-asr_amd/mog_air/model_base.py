@@ -137,6 +137,16 @@ class _Workspace:
         self.xb_fresh = False
         self.xb_ready = None
         self.dh_parts = None  # the K slices of a small batch's dh GEMM (DH_PARTS)
+        # cnn=True (AIR): the encoder's features (the LSTM input) and the
+        # pooled planes its backward reads; alloc_backward: dF and the
+        # per-workgroup partial sums of this batch size (a workspace is one
+        # batch size's: another batch gets another workspace)
+        self.feat = self.pool1 = self.pool2 = self.dF = self.cnn_part = None
+        if m.cnn:
+            F = m.cnn_filters
+            self.feat = e(B, m.lstm_in)
+            self.pool1 = e(B, ops.CNN_POOL1 ** 2 * F)
+            self.pool2 = e(B, ops.CNN_POOL2 ** 2 * F)
         self._bwd = False
         self.materialized = False
 
@@ -187,6 +197,9 @@ class _Workspace:
         self.dc = e(2, B, H)
         self.dG = e(T, B, 4 * H)
         self.dGsum = e(B, 4 * H)
+        if m.cnn:
+            self.dF = e(B, m.lstm_in)
+            self.cnn_part = e(ops.cnn_partial_elems(B))
         self._bwd = True
 
 
@@ -223,6 +236,7 @@ class ModelBase(GlimpseVAE, WeightGradients, GraphCapture, Results):
     _WORKSPACE = _Workspace
     num_prior = None
     marginal = None  # the ``-ap`` per-step prior bias (AIR only)
+    cnn = False      # the convolutional image encoder ahead of the LSTM (AIR only)
 
     def __init__(self, *, input_images, target_num_digits, max_steps, max_digits, rnn_units,
                  canvas_size, windows_size, vae_latent_dimensions, vae_recognition_units,
@@ -256,6 +270,9 @@ class ModelBase(GlimpseVAE, WeightGradients, GraphCapture, Results):
         self.rnn_units = int(rnn_units)
         self.canvas_size, self.windows_size = int(canvas_size), int(windows_size)
         self.C2, self.W2 = self.canvas_size ** 2, self.windows_size ** 2
+        # width of the LSTM's loop-invariant input: the canvas, or (AIR,
+        # cnn=True) the encoder's features
+        self.lstm_in = self.C2
         self.vae_latent_dimensions = int(vae_latent_dimensions)
         self.vae_recognition_units = tuple(vae_recognition_units)
         self.vae_generative_units = tuple(vae_generative_units)

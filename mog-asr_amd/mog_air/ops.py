@@ -298,6 +298,80 @@ def stn_backward(U: torch.Tensor, theta: torch.Tensor, out_hw, G: torch.Tensor,
     return dU, dtheta, dot
 
 
+CNN_CANVAS, CNN_POOL1, CNN_POOL2 = 50, 25, 12  # sides the encoder is compiled for
+
+
+def cnn_images_per_wg(B: int) -> int:
+    """Images one workgroup of the encoder backward sums at a batch of B by
+    default: B / 512 clamped to 1..8 (mog_cnn_enc_images_per_wg)."""
+    return int(_lib.load().mog_cnn_enc_images_per_wg(int(B)))
+
+
+def cnn_partial_elems(B: int, images_per_wg: Optional[int] = None) -> int:
+    """Floats of the encoder backward's per-workgroup partial sums for a
+    batch of B (mog_cnn_enc_partial_elems)."""
+    ipw = cnn_images_per_wg(B) if images_per_wg is None else int(images_per_wg)
+    return int(_lib.load().mog_cnn_enc_partial_elems(int(B), ipw))
+
+
+def _cnn_check(x, weights, B, F):
+    _chk(x, "x")
+    if x.shape != (B, CNN_CANVAS ** 2):
+        raise ValueError(f"x must be [{B}, {CNN_CANVAS ** 2}], got {tuple(x.shape)}")
+    shapes = ((5, 5, 1, F), (F,), (5, 5, F, F), (F,), (5, 5, F, F), (F,))
+    for t, s, n in zip(weights, shapes, ("w1", "b1", "w2", "b2", "w3", "b3")):
+        _chk(t, n)
+        if tuple(t.shape) != s:
+            raise ValueError(f"{n} must be {s}, got {tuple(t.shape)}")
+
+
+def cnn_enc_forward(x: torch.Tensor, weights: Sequence[torch.Tensor], pool1: torch.Tensor,
+                    pool2: torch.Tensor, feat: torch.Tensor) -> None:
+    """The cnn=True encoder (mog_cnn_enc_forward): x [B, 2500], weights =
+    (w1, b1, w2, b2, w3, b3) in HWIO -> feat [B, 144 F], with pool1
+    [B, 625 F] and pool2 [B, 144 F] kept for the backward."""
+    B, F = x.shape[0], weights[1].shape[0]
+    _cnn_check(x, weights, B, F)
+    for t, n, w in ((pool1, "pool1", CNN_POOL1 ** 2 * F), (pool2, "pool2", CNN_POOL2 ** 2 * F),
+                    (feat, "feat", CNN_POOL2 ** 2 * F)):
+        _chk(t, n)
+        if t.numel() != B * w:
+            raise ValueError(f"{n} must hold {B} x {w} elements, got {t.numel()}")
+    _ops.cnn_enc_forward_(x, *weights, B, F, pool1, pool2, feat)
+
+
+def cnn_enc_backward(x: torch.Tensor, weights: Sequence[torch.Tensor], pool1: torch.Tensor,
+                     pool2: torch.Tensor, feat: torch.Tensor, dF: torch.Tensor,
+                     part: torch.Tensor, grads: Sequence[torch.Tensor],
+                     images_per_wg: Optional[int] = None) -> None:
+    """The encoder's six gradients stored into grads = (gw1, gb1, gw2, gb2,
+    gw3, gb3) from dF [B, 144 F] (mog_cnn_enc_backward); images_per_wg
+    (1..8; default cnn_images_per_wg(B)): images a workgroup sums before it
+    stores its partial sums; part: scratch of cnn_partial_elems(B,
+    images_per_wg) floats.  Deterministic for one B and images_per_wg."""
+    B, F = x.shape[0], weights[1].shape[0]
+    ipw = cnn_images_per_wg(B) if images_per_wg is None else int(images_per_wg)
+    if not 1 <= ipw <= cnn_images_per_wg(1 << 30):
+        raise ValueError(f"images_per_wg must be 1..{cnn_images_per_wg(1 << 30)}, got {ipw}")
+    _cnn_check(x, weights, B, F)
+    for t, n, w in ((pool1, "pool1", CNN_POOL1 ** 2 * F), (pool2, "pool2", CNN_POOL2 ** 2 * F),
+                    (feat, "feat", CNN_POOL2 ** 2 * F), (dF, "dF", CNN_POOL2 ** 2 * F)):
+        _chk(t, n)
+        if t.numel() != B * w:
+            raise ValueError(f"{n} must hold {B} x {w} elements, got {t.numel()}")
+    _chk(part, "part")
+    if part.numel() < cnn_partial_elems(B, ipw):
+        raise ValueError(f"part holds {part.numel()} elements, a batch of {B} needs "
+                         f"{cnn_partial_elems(B, ipw)}")
+    for g, w in zip(grads, weights):
+        _chk(g, "grad")
+        if g.shape != w.shape:
+            raise ValueError(f"gradient of shape {tuple(g.shape)} for a tensor {tuple(w.shape)}")
+    w1, b1, w2, b2, w3, _ = weights
+    _ops.cnn_enc_backward_(x, w1, b1, w2, b2, w3, pool1, pool2, feat, dF, B, F, ipw, part,
+                           *grads)
+
+
 def _i64(v: int) -> int:
     """a 64-bit counter / seed as the signed int64 of an op schema's `int`"""
     v &= 2 ** 64 - 1

@@ -49,6 +49,29 @@ def param_specs(C2: int, H: int, W2: int, R: Tuple[int, int], G: Tuple[int, int]
     return specs
 
 
+CNN_LAYERS = ("conv1", "conv2", "conv3")
+
+
+def cnn_param_specs(F: int) -> List[Tuple[str, Tuple[int, ...]]]:
+    """The cnn=True image encoder's variables (air_model.py:763-810: three
+    tf.layers.conv2d under variable_scope("cnn"), kernels HWIO), appended
+    after param_specs so that every other variable keeps its offset and its
+    Glorot draw."""
+    p = "air/cnn/"
+    specs = []
+    for layer, cin in zip(CNN_LAYERS, (1, F, F)):
+        specs += [(p + layer + "/kernel", (5, 5, cin, F)), (p + layer + "/bias", (F,))]
+    return specs
+
+
+def glorot_limit(shape) -> float:
+    """The Glorot-uniform limit sqrt(6 / (fan_in + fan_out)) of a dense
+    [in, out] or convolution [h, w, in, out] kernel (TF's
+    glorot_uniform_initializer: the receptive field multiplies both fans)."""
+    field = int(np.prod(shape[:-2]))
+    return float(np.sqrt(6.0 / (field * (shape[-2] + shape[-1]))))
+
+
 class WeightCache:
     """Device buffers derived from the parameters (bf16 / fragment packs,
     transposed or split copies): each is built once and refreshed by its own
@@ -146,6 +169,9 @@ class ParamStore:
             n = int(np.prod(shape))
             if len(shape) == 2:
                 lim = np.sqrt(6.0 / (shape[0] + shape[1]))
+                host[o:o + n] = rng.uniform(-lim, lim, n).astype(np.float32)
+            elif len(shape) == 4:  # a convolution kernel (tf.layers.conv2d's default)
+                lim = glorot_limit(shape)
                 host[o:o + n] = rng.uniform(-lim, lim, n).astype(np.float32)
         self.flat.copy_(torch.from_numpy(host))
         self.version += 1

@@ -266,10 +266,11 @@ class WeightGradients:
     REC_WGRAD_X3 = True
 
     def _x_split3(self, X, ws):
-        """X in three exact bf16 pieces [3][B][C2p] (ws.X3): the A operand of
-        the pre-split x-rows gradient, split once per step in the forward's
-        prologue (X is the step's input, final before the x-projection)."""
-        B, C2 = ws.B, self.C2
+        """X (the LSTM's loop-invariant input, lstm_in wide) in three exact
+        bf16 pieces [3][B][C2p] (ws.X3): the A operand of the pre-split x-rows
+        gradient, split once per step in the forward's prologue (X is the
+        step's input, final before the x-projection)."""
+        B, C2 = ws.B, self.lstm_in
         C2p = self._pad8(C2)
         ops.split3_bf16(X, ws.buffer("X3", (3, B, C2p), torch.bfloat16), B, C2, C2, C2p, B * C2p)
 
@@ -282,8 +283,8 @@ class WeightGradients:
         accuracy) -- x3p: the pieces the model prepared in ws.X3 / ws.dG3;
         X_GRAD_X3 = 1: split inside the GEMM -- or the fp32 split-K chain.
         (The GEMM of every chunk is tagged; the operand conversions / splits
-        are other launches.)"""
-        B, H, C2 = ws.B, self.rnn_units, self.C2
+        are other launches.)  X is lstm_in wide."""
+        B, H, C2 = ws.B, self.rnn_units, self.lstm_in
         if self.precision == "bf16":
             return self._x_grad_bf16(X, ws, gK, bias_out, m0, m1)
         if not x3p and self.X_GRAD_X3 != 1:

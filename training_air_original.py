@@ -4,6 +4,7 @@
 lines, running the AIR train step on MI355X through mog_air.AIRModel.
 
     python training_air_original.py -dn 13 -ds 20k [--iterations N] [--precision bf16]
+                                    [--cnn 1 [--cnn_filters 8]]
 
 Model configuration: training_air_original.py:158-211 (max_steps 6, LSTM 256,
 VAE 784-512-256-50, scale prior -1 / 0.05, lr 1e-4, clip 1.0, z_pres prior
@@ -25,6 +26,10 @@ def main(argv=None):
     parser = argparse.ArgumentParser()
     trainer.add_common_args(parser, reader_threads=4)
     parser.add_argument("-ap", "--add_prior", type=str, default="")
+    # the reference model's conv encoder ahead of the LSTM (air_model.py:763-810;
+    # its scripts pass cnn=False): fp32, one device
+    parser.add_argument("--cnn", type=int, choices=(0, 1), default=0)
+    parser.add_argument("--cnn_filters", type=int, default=8)
     args = parser.parse_args(argv)
     args.add_prior = args.add_prior.lower() in ["true", "t", "1"]
     trainer.select_gpu(args.gpu)  # before the HIP runtime starts
@@ -59,7 +64,8 @@ def main(argv=None):
             vae_likelihood_std=0.3, scale_hidden_units=64, shift_hidden_units=64,
             z_pres_hidden_units=64, z_pres_prior_log_odds=-0.01, z_pres_temperature=1.0,
             stopping_threshold=0.99, learning_rate=1e-4, gradient_clipping_norm=1.0,
-            cnn=False, cnn_filters=8, num_summary_images=NUM_IMAGES_TO_SAVE,
+            cnn=bool(args.cnn), cnn_filters=args.cnn_filters,
+            num_summary_images=NUM_IMAGES_TO_SAVE,
             train=(i == 0), reuse=(i == 1), scope="air",
             annealing_schedules={"z_pres_prior_log_odds": {
                 "init": 10000.0, "min": 0.000000001, "factor": 0.1, "iters": 3000,
