@@ -666,6 +666,37 @@ int mog_copy32_batch(int nbuf, void* const* dst, const void* const* src, const l
 int mog_transpose32_batch(int nbuf, float* const* dst, const float* const* src, const int* rows,
                           const int* cols, void* stream);
 
+/* ---- detection metrics on the device (evaluation_detection.py:28-98) -------
+ * mog_air/evaluation.py:42-78 for n images at once, in float64.  gt_boxes
+ * [N][G][4] = [x, y, x + w, y + h], gt_num [N] (G <= 8); this chunk is images
+ * [offset, offset + n) of them.  Detection d of chunk image i is shifts[i
+ * shift_image_stride + d shift_step_stride + {0, 1}] and scales[i
+ * scale_image_stride + d scale_step_stride] (element strides; fp32, or fp64
+ * with f64 != 0), so the models' step-major buffers are read in place; rows
+ * d >= steps read as zero (steps <= T <= 8), det_num [n] is clamped to
+ * [0, T].  thresholds: 11 doubles on the device, the values of
+ * evaluation.THRESHOLDS (compared, never recomputed).  Every IoU is the
+ * host's bits (one rounding per operation, no contraction).  per_image
+ * [N][25], rows [offset, offset + n) written: precision[11], recall[11], gt
+ * best-IoU, detection best-IoU, global (optimally assigned) IoU. */
+int mog_eval_detection(const double* gt_boxes, const int* gt_num, int G, const void* shifts,
+                       const void* scales, int f64, long shift_image_stride,
+                       long shift_step_stride, long scale_image_stride, long scale_step_stride,
+                       const int* det_num, int n, int T, int steps, double csize,
+                       const double* thresholds, double* per_image, int offset, void* stream);
+/* means[25] = column means of per_image [N][25], summed in an order fixed by
+ * N alone (no atomics): the same bits on every run. */
+int mog_eval_detection_means(const double* per_image, int N, double* means, void* stream);
+
+/* ---- device-resident batch feed --------------------------------------------
+ * out[b, :] = src[idx[b], :] (fp32 rows of `width` floats, b < B) and, when
+ * ksrc / kout are given (both or neither), kout[b] = ksrc[idx[b]], in one
+ * launch; idx int32 on the device, every entry in [0, rows) (an entry outside
+ * copies nothing).  16-byte accesses when width % 4 == 0 and src / out are
+ * 16-byte aligned, dwords otherwise. */
+int mog_gather_rows(const float* src, const int* ksrc, const int* idx, int rows, int width,
+                    int B, float* out, int* kout, void* stream);
+
 /* ---- measurement instrument (no reference counterpart) -------------------
  * dst[i] = src[i] for n4 float4s (16-byte aligned): the copy bandwidth the
  * bench quotes beside the HBM spec.  (The test-only instruments mog_spin and

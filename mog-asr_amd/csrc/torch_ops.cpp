@@ -362,6 +362,66 @@ void cnn_enc_backward_(const Tensor& x, const Tensor& w1, const Tensor& b1, cons
         o.name);
 }
 
+// --------------------------------- detection metrics, device batch feed ----
+// (mog_eval_detection / mog_eval_detection_means / mog_gather_rows; strides
+// in elements of the detections' dtype, fp32 or fp64)
+void eval_detection_(const Tensor& gt_boxes, const Tensor& gt_num, int64_t N, int64_t G,
+                     const Tensor& shifts, const Tensor& scales, int64_t shift_image_stride,
+                     int64_t shift_step_stride, int64_t scale_image_stride,
+                     int64_t scale_step_stride, const Tensor& det_num, int64_t n, int64_t T,
+                     int64_t steps, double csize, const Tensor& thresholds, Tensor per_image,
+                     int64_t offset) {
+  Op o("eval_detection_");
+  TORCH_CHECK(n >= 0 && offset >= 0 && offset + n <= N && G >= 1 && G <= 8 && T >= 0 && T <= 8 &&
+                  steps >= 0 && steps <= T,
+              o.name, ": bad extents (G, T <= 8; steps <= T; offset + n <= N)");
+  TORCH_CHECK(shift_image_stride >= 0 && shift_step_stride >= 0 && scale_image_stride >= 0 &&
+                  scale_step_stride >= 0,
+              o.name, ": negative stride");
+  const ScalarType dt = shifts.scalar_type();
+  TORCH_CHECK(dt == F32 || dt == at::kDouble, o.name, ": shifts must be float32 or float64");
+  double* pp = static_cast<double*>(o.need(per_image, at::kDouble, N * 25, "per_image"));
+  void* pb = o.need(gt_boxes, at::kDouble, N * G * 4, "gt_boxes");
+  int* pg = o.i(gt_num, N, "gt_num");
+  const bool rows = n > 0 && steps > 0;
+  void* psh = o.need(shifts, dt,
+                     rows ? (n - 1) * shift_image_stride + (steps - 1) * shift_step_stride + 2 : 0,
+                     "shifts");
+  void* psc = o.need(scales, dt,
+                     rows ? (n - 1) * scale_image_stride + (steps - 1) * scale_step_stride + 1 : 0,
+                     "scales");
+  int* pd = o.i(det_num, n, "det_num");
+  void* pt = o.need(thresholds, at::kDouble, 11, "thresholds");
+  GUARD(o);
+  check(mog_eval_detection(static_cast<const double*>(pb), pg, (int)G, psh, psc,
+                           dt == at::kDouble, shift_image_stride, shift_step_stride,
+                           scale_image_stride, scale_step_stride, pd, (int)n, (int)T, (int)steps,
+                           csize, static_cast<const double*>(pt), pp, (int)offset, o.stream()),
+        o.name);
+}
+
+void eval_detection_means_(const Tensor& per_image, int64_t N, Tensor means) {
+  Op o("eval_detection_means_");
+  TORCH_CHECK(N >= 1, o.name, ": N");
+  double* pm = static_cast<double*>(o.need(means, at::kDouble, 25, "means"));
+  void* pp = o.need(per_image, at::kDouble, N * 25, "per_image");
+  GUARD(o);
+  check(mog_eval_detection_means(static_cast<const double*>(pp), (int)N, pm, o.stream()), o.name);
+}
+
+void gather_rows_(const Tensor& src, const optional<Tensor>& ksrc, const Tensor& idx, int64_t rows,
+                  int64_t width, int64_t B, Tensor out, const optional<Tensor>& kout) {
+  Op o("gather_rows_");
+  TORCH_CHECK(rows >= 0 && width >= 1 && B >= 0, o.name, ": bad shape");
+  float* po = o.f(out, B * width, "out");
+  int* pko = o.i(kout, B, "kout");
+  float* ps = o.f(src, rows * width, "src");
+  int* pks = o.i(ksrc, rows, "ksrc");
+  int* pi = o.i(idx, B, "idx");
+  GUARD(o);
+  check(mog_gather_rows(ps, pks, pi, (int)rows, (int)width, (int)B, po, pko, o.stream()), o.name);
+}
+
 // ----------------------------------------------------------------- LSTM ----
 void lstm_cell_forward_(const Tensor& G, const optional<Tensor>& bias,
                         const optional<Tensor>& c_prev, Tensor c_out, Tensor h_out, int64_t B,
@@ -1706,6 +1766,15 @@ TORCH_LIBRARY_FRAGMENT(mog_air, m) {
       "Tensor(g!) zval, Tensor(h!) zmask) -> ()");
   m.def("bernoulli_threshold_(Tensor x, Tensor u, Tensor(a!) out, int n) -> ()");
   m.def(
+      "eval_detection_(Tensor gt_boxes, Tensor gt_num, int N, int G, Tensor shifts, "
+      "Tensor scales, int shift_image_stride, int shift_step_stride, int scale_image_stride, "
+      "int scale_step_stride, Tensor det_num, int n, int T, int steps, float csize, "
+      "Tensor thresholds, Tensor(a!) per_image, int offset) -> ()");
+  m.def("eval_detection_means_(Tensor per_image, int N, Tensor(a!) means) -> ()");
+  m.def(
+      "gather_rows_(Tensor src, Tensor? ksrc, Tensor idx, int rows, int width, int B, "
+      "Tensor(a!) out, Tensor(b!)? kout) -> ()");
+  m.def(
       "asr_terms_(int B, int T, int C, int[] cons, float[] gammas, Tensor rec, Tensor vkl, "
       "Tensor zmask, Tensor live, Tensor(a!) klsum, Tensor(b!) pr, Tensor(c!) area, "
       "Tensor(d!) out, Tensor(e!) size, Tensor(f!) overlap, Tensor(g!) zsum) -> ()");
@@ -1785,6 +1854,9 @@ TORCH_LIBRARY_IMPL(mog_air, CUDA, m) {
   m.impl("asr_step_backward_learned_", &asr_step_backward_learned_);
   m.impl("asr_gen_step_learned_", &asr_gen_step_learned_);
   m.impl("bernoulli_threshold_", &bernoulli_threshold_);
+  m.impl("eval_detection_", &eval_detection_);
+  m.impl("eval_detection_means_", &eval_detection_means_);
+  m.impl("gather_rows_", &gather_rows_);
   m.impl("asr_terms_", &asr_terms_);
   m.impl("asr_finalize_", &asr_finalize_);
   m.impl("asr_terms_backward_", &asr_terms_backward_);

@@ -105,6 +105,9 @@ _SIGS = {
     "mog_cnn_enc_partial_elems": [I, I],
     "mog_cnn_enc_forward": [P] * 7 + [I, I, P, P, P, P],
     "mog_cnn_enc_backward": [P] * 10 + [I, I, I, P, L] + [P] * 7,
+    "mog_eval_detection": [P, P, I, P, P, I, L, L, L, L, P, I, I, I, ctypes.c_double, P, P, I, P],
+    "mog_eval_detection_means": [P, I, P, P],
+    "mog_gather_rows": [P, P, P, I, I, I, P, P, P],
 }
 
 # entry points that do not return an int status

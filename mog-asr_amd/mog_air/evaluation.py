@@ -76,3 +76,77 @@ def evaluation(gt_position_xy, gt_scale_xy, inf_shifts, inf_scales, inf_num, csi
         global_iou[i] = iou[r, c].sum() / max(n_det, n_gt)
     return (precision.mean(0), recall.mean(0), gt_best.mean(), det_best.mean(),
             global_iou.mean())
+
+
+EVAL_CAP = 8  # ground-truth boxes / loop steps per image of the device kernel (csrc/eval_det.hip)
+
+
+def gt_box_table(gt_position_xy, gt_scale_xy):
+    """(boxes [N, G, 4] float64 = [x, y, x + w, y + h], counts [N] int32) of
+    the per-image lists, as ``evaluation`` builds each image's boxes (xy +
+    size in float64, list order); G = the largest count (at least 1), unused
+    slots zero."""
+    n_img = len(gt_position_xy)
+    num = np.asarray([len(p) // 2 for p in gt_position_xy], np.int32).reshape(n_img)
+    G = max(1, int(num.max()) if n_img else 1)
+    boxes = np.zeros((n_img, G, 4), np.float64)
+    for i in range(n_img):
+        g = int(num[i])
+        if g:
+            xy = np.asarray(gt_position_xy[i], np.float64)[:2 * g].reshape(-1, 2)
+            size = np.asarray(gt_scale_xy[i], np.float64).reshape(-1, 2)
+            boxes[i, :g] = np.concatenate([xy, xy + size], axis=1)
+    return boxes, num
+
+
+class DeviceEvaluator:
+    """``evaluation`` on the device (ops.eval_detection): the ground-truth
+    boxes are uploaded once; ``update`` takes each chunk's detections as
+    device tensors (the test model's rec_shifts / rec_scales views are read in
+    place) without a host synchronisation; ``result`` is the 5-tuple of
+    ``evaluation`` after one 25-double copy.  At most EVAL_CAP boxes per image
+    and EVAL_CAP loop steps (ValueError above either)."""
+
+    def __init__(self, gt_position_xy, gt_scale_xy, csize, device, max_steps: int = EVAL_CAP):
+        import torch
+
+        from . import ops
+        assert ops.EVAL_CAP == EVAL_CAP
+        boxes, num = gt_box_table(gt_position_xy, gt_scale_xy)
+        if boxes.shape[1] > EVAL_CAP:
+            raise ValueError(f"{boxes.shape[1]} ground-truth boxes in one image: the device "
+                             f"metrics hold {EVAL_CAP}")
+        if not 0 <= max_steps <= EVAL_CAP:
+            raise ValueError(f"max_steps {max_steps}: the device metrics hold {EVAL_CAP}")
+        self._ops, self.csize, self.max_steps = ops, float(csize), int(max_steps)
+        self.n_images = boxes.shape[0]
+        self.gt_boxes = torch.from_numpy(boxes).to(device)
+        self.gt_num = torch.from_numpy(num).to(device)
+        self.thresholds = torch.from_numpy(np.ascontiguousarray(THRESHOLDS, np.float64)).to(device)
+        self._per_image = torch.zeros((self.n_images, ops.EVAL_COLUMNS), dtype=torch.float64,
+                                      device=device)
+        self._means = torch.zeros(ops.EVAL_COLUMNS, dtype=torch.float64, device=device)
+
+    def update(self, offset: int, rec_shifts, rec_scales, rec_num) -> None:
+        """Images [offset, offset + n): rec_shifts [n, steps, 2], rec_scales
+        [n, steps(, 1)] (fp32 or fp64, any strides), rec_num [n] int32."""
+        if rec_shifts.dim() == 3 and rec_shifts.shape[1] > self.max_steps:
+            raise ValueError(f"{rec_shifts.shape[1]} loop steps, the evaluator was built for "
+                             f"{self.max_steps}")
+        self._ops.eval_detection(self.gt_boxes, self.gt_num, rec_shifts, rec_scales, rec_num,
+                                 self.csize, self.thresholds, self._per_image, offset=offset,
+                                 max_steps=self.max_steps)
+
+    def per_image(self):
+        """[N, 25] float64 on the device: precision[11], recall[11], gt
+        best-IoU, detection best-IoU, global IoU of every image."""
+        return self._per_image
+
+    def means(self):
+        """The 25 batch means on the device (a fixed summation order)."""
+        self._ops.eval_detection_means(self._per_image, self._means)
+        return self._means
+
+    def result(self):
+        m = self.means().cpu().numpy()
+        return m[:11].copy(), m[11:22].copy(), float(m[22]), float(m[23]), float(m[24])

@@ -372,6 +372,109 @@ def cnn_enc_backward(x: torch.Tensor, weights: Sequence[torch.Tensor], pool1: to
                            *grads)
 
 
+EVAL_CAP = 8      # boxes / loop steps per image of the metrics kernel (= evaluation.EVAL_CAP)
+EVAL_COLUMNS = 25  # precision[11], recall[11], gt best-IoU, detection best-IoU, global IoU
+
+
+def eval_detection(gt_boxes: torch.Tensor, gt_num: torch.Tensor, shifts: torch.Tensor,
+                   scales: torch.Tensor, det_num: torch.Tensor, csize: float,
+                   thresholds: torch.Tensor, per_image: torch.Tensor, offset: int = 0,
+                   max_steps: Optional[int] = None) -> None:
+    """Detection metrics of images [offset, offset + n) of a test set
+    (mog_eval_detection): gt_boxes [N, G, 4] float64, gt_num [N] int32, shifts
+    [n, steps, 2] and scales [n, steps] or [n, steps, 1] (float32 or float64,
+    any image / step strides: the models' transposed views are read in place),
+    det_num [n] int32, thresholds = evaluation.THRESHOLDS on the device ->
+    per_image [N, 25] float64, rows [offset, offset + n).  Detections at or
+    beyond `steps` are zero rows; det_num is clamped to max_steps (default
+    `steps`).  G, max_steps <= 8."""
+    _chk(gt_boxes, "gt_boxes", torch.float64)
+    _chk(gt_num, "gt_num", torch.int32)
+    _chk(per_image, "per_image", torch.float64)
+    _chk(thresholds, "thresholds", torch.float64)
+    _chk(det_num, "det_num", torch.int32)
+    if gt_boxes.dim() != 3 or gt_boxes.shape[2] != 4:
+        raise ValueError(f"gt_boxes must be [N, G, 4], got {tuple(gt_boxes.shape)}")
+    N, G = gt_boxes.shape[0], gt_boxes.shape[1]
+    if shifts.dim() != 3 or shifts.shape[2] != 2:
+        raise ValueError(f"shifts must be [n, steps, 2], got {tuple(shifts.shape)}")
+    n, steps = shifts.shape[0], shifts.shape[1]
+    T = steps if max_steps is None else int(max_steps)
+    if not 1 <= G <= EVAL_CAP:
+        raise ValueError(f"{G} ground-truth boxes per image: the kernel holds 1..{EVAL_CAP}")
+    if T > EVAL_CAP or steps > T:
+        raise ValueError(f"{steps} step rows of at most {T}: the kernel holds {EVAL_CAP} "
+                         "and steps <= max_steps")
+    if scales.dim() == 3 and scales.shape[2] == 1:
+        scales = scales[:, :, 0]
+    for t, name in ((shifts, "shifts"), (scales, "scales")):
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a HIP device tensor")
+        if t.dtype not in (torch.float32, torch.float64) or t.dtype != shifts.dtype:
+            raise ValueError(f"{name} must be float32 or float64 (both alike), got {t.dtype}")
+    if tuple(scales.shape) != (n, steps):
+        raise ValueError(f"scales must be [{n}, {steps}(, 1)], got {tuple(scales.shape)}")
+    if steps and n and shifts.stride(2) != 1:
+        raise ValueError("the two shift components must be adjacent in memory")
+    if min(shifts.stride()[:2] + scales.stride()) < 0:
+        raise ValueError("negative strides")
+    if tuple(gt_num.shape) != (N,) or tuple(det_num.shape) != (n,):
+        raise ValueError(f"gt_num must be [{N}] and det_num [{n}]")
+    if tuple(per_image.shape) != (N, EVAL_COLUMNS) or thresholds.numel() != 11:
+        raise ValueError(f"per_image must be [{N}, {EVAL_COLUMNS}] and thresholds hold 11 values")
+    if offset < 0 or offset + n > N:
+        raise ValueError(f"images [{offset}, {offset + n}) of a test set of {N}")
+    _ops.eval_detection_(gt_boxes, gt_num, N, G, shifts, scales, shifts.stride(0),
+                         shifts.stride(1), scales.stride(0), scales.stride(1), det_num, n, T,
+                         steps, float(csize), thresholds, per_image, int(offset))
+
+
+def eval_detection_means(per_image: torch.Tensor, means: torch.Tensor) -> None:
+    """means [25] = the column means of per_image [N, 25] float64 in an order
+    fixed by N (mog_eval_detection_means): the same bits on every run."""
+    _chk(per_image, "per_image", torch.float64)
+    _chk(means, "means", torch.float64)
+    if per_image.dim() != 2 or per_image.shape[1] != EVAL_COLUMNS or per_image.shape[0] < 1:
+        raise ValueError(f"per_image must be [N >= 1, {EVAL_COLUMNS}], got "
+                         f"{tuple(per_image.shape)}")
+    if means.numel() != EVAL_COLUMNS:
+        raise ValueError(f"means must hold {EVAL_COLUMNS} values, got {means.numel()}")
+    _ops.eval_detection_means_(per_image, per_image.shape[0], means)
+
+
+def gather_rows(src: torch.Tensor, idx, out: torch.Tensor, ksrc: Optional[torch.Tensor] = None,
+                kout: Optional[torch.Tensor] = None) -> None:
+    """out[b] = src[idx[b]] for the B picks of `idx` (and kout[b] =
+    ksrc[idx[b]], int32, in the same launch; mog_gather_rows).  `idx`: a host
+    sequence / array / CPU tensor of row numbers, checked against src's rows
+    here (ValueError, no launch) and uploaded as int32.  Rows of `out` at or
+    beyond B are left alone."""
+    _chk(src, "src")
+    _chk(out, "out")
+    if src.dim() != 2 or out.dim() != 2 or out.shape[1] != src.shape[1]:
+        raise ValueError(f"src [rows, width] and out [>= B, width], got {tuple(src.shape)} and "
+                         f"{tuple(out.shape)}")
+    if isinstance(idx, torch.Tensor) and idx.is_cuda:
+        raise ValueError("idx must be on the host: it is range-checked before the launch")
+    host = torch.as_tensor(idx).reshape(-1)
+    if host.dtype.is_floating_point or host.dtype == torch.bool:
+        raise ValueError(f"idx must be integers, got {host.dtype}")
+    B, rows, width = host.numel(), src.shape[0], src.shape[1]
+    if B and (int(host.min()) < 0 or int(host.max()) >= rows):
+        raise ValueError(f"idx outside [0, {rows})")
+    if out.shape[0] < B:
+        raise ValueError(f"out holds {out.shape[0]} rows, idx picks {B}")
+    if (ksrc is None) != (kout is None):
+        raise ValueError("ksrc and kout go together")
+    if ksrc is not None:
+        _chk(ksrc, "ksrc", torch.int32)
+        _chk(kout, "kout", torch.int32)
+        if ksrc.numel() != rows or kout.numel() < B:
+            raise ValueError(f"ksrc must hold {rows} values and kout at least {B}")
+    dev_idx = host.to(torch.int32).to(src.device)
+    _ops.gather_rows_(src, ksrc, dev_idx, rows, width, B, out, kout)
+
+
 def _i64(v: int) -> int:
     """a 64-bit counter / seed as the signed int64 of an op schema's `int`"""
     v &= 2 ** 64 - 1

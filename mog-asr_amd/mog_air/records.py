@@ -311,7 +311,8 @@ class ShuffleBatcher:
             except StopIteration:
                 self._exhausted = True
 
-    def next_batch(self) -> Tuple[np.ndarray, np.ndarray]:
+    def next_indices(self) -> np.ndarray:
+        """The dataset rows of the next batch (what ``next_batch`` gathers)."""
         self._fill()
         if len(self._buf) < self.batch_size:
             raise StopIteration
@@ -320,5 +321,45 @@ class ShuffleBatcher:
             j = int(self.rng.integers(len(self._buf)))
             self._buf[j], self._buf[-1] = self._buf[-1], self._buf[j]
             picks.append(self._buf.pop())
-        idx = np.asarray(picks)
+        return np.asarray(picks)
+
+    def next_batch(self) -> Tuple[np.ndarray, np.ndarray]:
+        idx = self.next_indices()
         return self.images[idx], self.digits[idx].astype(np.int32)
+
+
+class DeviceFeed:
+    """``ShuffleBatcher`` over a dataset held on the device: the images and
+    digit counts are uploaded once, every batch is the picks of the same
+    shuffle (same seed, same RNG draws, same StopIteration) gathered by one
+    kernel launch (ops.gather_rows).  ``next_batch`` returns this rank's
+    contiguous shard (parallel.shard) of the global batch as device tensors
+    (x [b, C*C] float32, k [b] int32) and the global batch size; only the
+    shard's rows are gathered.  Every batch is a pair of fresh tensors, so a
+    step still reading the previous batch is never overwritten."""
+
+    def __init__(self, images: np.ndarray, digits: np.ndarray, batch_size: int,
+                 num_epochs: Optional[int], min_after_dequeue: int = 10000, seed: int = 12345,
+                 device="cuda:0", rank: int = 0, world: int = 1):
+        import torch
+
+        from . import ops
+        from .parallel import shard
+        self._torch, self._ops = torch, ops
+        self.device = torch.device(device)
+        images = np.ascontiguousarray(images, np.float32)
+        self.images = torch.from_numpy(images.reshape(len(images), -1)).to(self.device)
+        self.digits = torch.from_numpy(np.ascontiguousarray(digits, np.int32)).to(self.device)
+        # the shuffle needs only the dataset's length
+        self._picks = ShuffleBatcher(np.empty((len(digits), 0), np.float32), np.asarray(digits),
+                                     batch_size, num_epochs, min_after_dequeue, seed)
+        self._lo, self._hi = shard(batch_size, rank, world)
+        self.batch_size = batch_size
+
+    def next_batch(self):
+        idx = self._picks.next_indices()[self._lo:self._hi]
+        torch = self._torch
+        x = torch.empty((len(idx), self.images.shape[1]), dtype=torch.float32, device=self.device)
+        k = torch.empty((len(idx),), dtype=torch.int32, device=self.device)
+        self._ops.gather_rows(self.images, idx, x, ksrc=self.digits, kout=k)
+        return x, k, self.batch_size

@@ -39,7 +39,7 @@ def add_common_args(parser, reader_threads: int):
     """The CLI flags shared by both entry points (training_air_original.py:49-60,
     train_air_pr.py:40-61) plus this framework's options (not in the
     reference): --iterations, --precision, --test-batch, --synth-per-count,
-    --write-synthetic, --device."""
+    --write-synthetic, --device, --resident."""
     parser.add_argument("-r", "--results-folder", default="Not Valid")
     parser.add_argument("-k", "-key", "--key", default="")
     parser.add_argument("-gpu", "--gpu", default="-1")
@@ -58,6 +58,10 @@ def add_common_args(parser, reader_threads: int):
                         help="images per object count when the dataset files are absent")
     parser.add_argument("--write-synthetic", type=int, choices=[0, 1], default=0)
     parser.add_argument("--device", default="cuda:0")
+    parser.add_argument("--resident", type=int, choices=[0, 1], default=0,
+                        help="1: the datasets live on the device -- batches gathered there "
+                             "(records.DeviceFeed), detection metrics computed there "
+                             "(evaluation.DeviceEvaluator)")
     parser.add_argument("--no-images", action="store_true",
                         help="skip the PNG grids (training_air_original.py:368-411)")
 
@@ -266,10 +270,74 @@ class Saver:
         return path
 
 
-def run_test(test_model, test, canvas: int, batch: int):
+def resident_ok(args, tr_x, test, test_model, log) -> bool:
+    """--resident 1 is taken only when both datasets fit in half of the
+    device's free memory and the test set is within the metrics kernel's caps
+    (boxes per image, loop steps); otherwise one warning and the host path."""
+    if not getattr(args, "resident", 0):
+        return False
+    import torch
+
+    from .evaluation import EVAL_CAP
+    need = int(np.asarray(tr_x).nbytes) + int(np.asarray(test[0]).nbytes)
+    free = torch.cuda.mem_get_info(torch.device(args.device))[0]
+    boxes = max([len(p) // 2 for p in test[3]], default=0)
+    why = None
+    if need > free // 2:
+        why = "the datasets take %d bytes, more than half of the %d free" % (need, free)
+    elif boxes > EVAL_CAP or test_model.max_steps > EVAL_CAP:
+        why = "%d boxes per image / %d loop steps exceed the device metrics' cap of %d" % (
+            boxes, test_model.max_steps, EVAL_CAP)
+    if why is not None:
+        log.warning("--resident 1 not taken (%s): host feed and host metrics", why)
+        return False
+    return True
+
+
+class _HostFeed:
+    """The host input pipeline: ShuffleBatcher batches, sharded per rank."""
+
+    def __init__(self, tr_x, tr_k, ctx):
+        self.ctx = ctx
+        self.batcher = records.ShuffleBatcher(tr_x, tr_k, BATCH_SIZE, EPOCHS,
+                                              min_after_dequeue=min(10000, len(tr_k)))
+
+    def next_batch(self):
+        xg, kg = self.batcher.next_batch()
+        x, k = self.ctx.shard(xg, kg)
+        return x, k, len(kg)
+
+
+def make_feed(args, tr_x, tr_k, ctx, resident: bool):
+    """(x, k, global batch size) per ``next_batch()``: this rank's shard of
+    the shuffled batch, host arrays or (resident) device tensors."""
+    if not resident:
+        return _HostFeed(tr_x, tr_k, ctx)
+    return records.DeviceFeed(tr_x, tr_k, BATCH_SIZE, EPOCHS,
+                              min_after_dequeue=min(10000, len(tr_k)), device=args.device,
+                              rank=ctx.rank, world=ctx.world)
+
+
+def resident_test_set(args, test, canvas: int, test_model):
+    """The test images and digit counts on the device (the per-object lists
+    stay on the host) and the evaluator holding the ground-truth boxes."""
+    import torch
+
+    from .evaluation import DeviceEvaluator
+    dev = torch.device(args.device)
+    images = torch.from_numpy(np.ascontiguousarray(test[0], np.float32)).to(dev)
+    digits = torch.from_numpy(np.ascontiguousarray(test[1], np.int32)).to(dev)
+    evaluator = DeviceEvaluator(test[3], test[4], canvas, dev, max_steps=test_model.max_steps)
+    return (images, digits) + tuple(test[2:]), evaluator
+
+
+def run_test(test_model, test, canvas: int, batch: int, evaluator=None):
     """Test-model fetches over the whole test set: (loss, accuracy, mse,
     rec_scales, rec_shifts, rec_num_digits), batched when `batch` > 0 and
-    combined as the batch means the reference computes in one run."""
+    combined as the batch means the reference computes in one run.  With an
+    ``evaluator`` (evaluation.DeviceEvaluator; test[0] / test[1] device
+    tensors) every chunk's detections go to it in place and (loss, accuracy,
+    mse, evaluator) is returned."""
     images, digits = test[0], test[1]
     n = len(digits)
     step = batch if batch > 0 else n
@@ -283,6 +351,10 @@ def run_test(test_model, test, canvas: int, batch: int):
         loss += test_model.loss * w
         acc += test_model.accuracy * w
         mse += test_model.mse_loss * w
+        if evaluator is not None:
+            evaluator.update(s, test_model.rec_shifts, test_model.rec_scales,
+                             test_model.rec_num_digits)
+            continue
         sc = np.zeros((len(k), T, 1), np.float32)
         sh = np.zeros((len(k), T, 2), np.float32)
         rs, rh = test_model.rec_scales.cpu().numpy(), test_model.rec_shifts.cpu().numpy()
@@ -291,6 +363,8 @@ def run_test(test_model, test, canvas: int, batch: int):
         scales.append(sc)
         shifts.append(sh)
         nums.append(test_model.rec_num_digits.cpu().numpy())
+    if evaluator is not None:
+        return loss, acc, mse, evaluator
     return loss, acc, mse, np.concatenate(scales), np.concatenate(shifts), np.concatenate(nums)
 
 
@@ -300,8 +374,10 @@ def train_loop(args, train_model, test_model, tr_x, tr_k, test, canvas, log, mod
     20, testing every 200, parameters every 10,000 iterations; the final
     test when the input runs out)."""
     ctx = ctx or Dist()
-    batcher = records.ShuffleBatcher(tr_x, tr_k, BATCH_SIZE, EPOCHS,
-                                     min_after_dequeue=min(10000, len(tr_k)))
+    resident = resident_ok(args, tr_x, test, test_model, log)
+    feed = make_feed(args, tr_x, tr_k, ctx, resident)
+    test_dev, evaluator = (resident_test_set(args, test, canvas, test_model)
+                           if resident and ctx.main else (None, None))
     saver = Saver(models_folder, "air-model")
     min_loss, update_flag = 9999999.0, False
     best = [0.0, 0.0, 0.0, 0.0]
@@ -313,11 +389,17 @@ def train_loop(args, train_model, test_model, tr_x, tr_k, test, canvas, log, mod
         if not ctx.main:
             ctx.barrier()
             return 0.0, 0.0, 0.0, 0.0
-        tl, ta, tm, sc, sh, nd = run_test(test_model, test, canvas, args.test_batch)
+        if evaluator is not None:
+            tl, ta, tm, _ = run_test(test_model, test_dev, canvas, args.test_batch, evaluator)
+        else:
+            tl, ta, tm, sc, sh, nd = run_test(test_model, test, canvas, args.test_batch)
         ctx.barrier()
         log.info("iteration {}\ttest loss {:.3f}\ttest accuracy {:.2f}, test mse {:.3f}".format(
             tag, tl, ta, tm))
-        p, r, gt_iou, det_iou, g_iou = evaluation(test[3], test[4], sh, sc, nd, csize=canvas)
+        if evaluator is not None:
+            p, r, gt_iou, det_iou, g_iou = evaluator.result()
+        else:
+            p, r, gt_iou, det_iou, g_iou = evaluation(test[3], test[4], sh, sc, nd, csize=canvas)
         # integer steps are padded to 6 as training_air_original.py:357 does
         # ('final' is printed as is)
         step_tag = "{:6d}".format(tag) if isinstance(tag, int) else tag
@@ -342,9 +424,8 @@ def train_loop(args, train_model, test_model, tr_x, tr_k, test, canvas, log, mod
         while True:
             if step % SAVE_PARAMS_EACH_ITERATIONS == 0 and ctx.main:
                 saver.save(train_model.params, step)
-            xg, kg = batcher.next_batch()
-            x, k = ctx.shard(xg, kg)
-            loss, acc, mse, step = train_model.step(x, k, global_batch=len(kg))
+            x, k, nglobal = feed.next_batch()
+            loss, acc, mse, step = train_model.step(x, k, global_batch=nglobal)
             if extra_log is not None:
                 extra_log(train_model, step)
             hist.append([loss, acc, mse])
@@ -386,8 +467,10 @@ def train_loop_asr(args, train_model, test_model, tr_x, tr_k, test, canvas, log,
     metrics); parameters are saved every 10,000 iterations; the final test
     when the input runs out.  Data parallel as train_loop."""
     ctx = ctx or Dist()
-    batcher = records.ShuffleBatcher(tr_x, tr_k, BATCH_SIZE, EPOCHS,
-                                     min_after_dequeue=min(10000, len(tr_k)))
+    resident = resident_ok(args, tr_x, test, test_model, log)
+    feed = make_feed(args, tr_x, tr_k, ctx, resident)
+    test_dev, evaluator = (resident_test_set(args, test, canvas, test_model)
+                           if resident and ctx.main else (None, None))
     saver = Saver(models_folder, "air-model")
     min_loss, update_flag = 9999999.0, False
     best = [0.0, 0.0, 0.0, 0.0]
@@ -399,9 +482,14 @@ def train_loop_asr(args, train_model, test_model, tr_x, tr_k, test, canvas, log,
         if not ctx.main:
             ctx.barrier()
             return
-        tl, ta, tm, sc, sh, nd = run_test(test_model, test, canvas, args.test_batch)
-        ctx.barrier()
-        p, r, gt_iou, det_iou, g_iou = evaluation(test[3], test[4], sh, sc, nd, csize=canvas)
+        if evaluator is not None:
+            run_test(test_model, test_dev, canvas, args.test_batch, evaluator)
+            ctx.barrier()
+            p, r, gt_iou, det_iou, g_iou = evaluator.result()
+        else:
+            tl, ta, tm, sc, sh, nd = run_test(test_model, test, canvas, args.test_batch)
+            ctx.barrier()
+            p, r, gt_iou, det_iou, g_iou = evaluation(test[3], test[4], sh, sc, nd, csize=canvas)
         log.info("test:{:6d}\tprecision:{}\trecall:{}\tgtIoU:{:.4f}\tdetectionIoU:{:.4f}"
                  "\tglobal_iou:{:.4f}".format(tag, p, r, gt_iou, det_iou, g_iou))
         lv = test_model.log_variables
@@ -429,9 +517,8 @@ def train_loop_asr(args, train_model, test_model, tr_x, tr_k, test, canvas, log,
         while True:
             if step % SAVE_PARAMS_EACH_ITERATIONS == 0 and ctx.main:
                 saver.save(train_model.params, step)
-            xg, kg = batcher.next_batch()
-            x, k = ctx.shard(xg, kg)
-            _, _, _, step = train_model.step(x, k, global_batch=len(kg))
+            x, k, nglobal = feed.next_batch()
+            _, _, _, step = train_model.step(x, k, global_batch=nglobal)
             for n, v in train_model.log_variables.items():
                 logged.setdefault(n, []).append(v)
             if step % LOG_EACH_ITERATION == 0:
