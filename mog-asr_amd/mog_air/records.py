@@ -18,6 +18,7 @@ field 1 (bytes repeated; floats / int64 packed, unpacked also accepted).
 from __future__ import annotations
 
 import struct
+import zlib
 from typing import Dict, Iterator, List, Optional, Tuple
 
 import numpy as np
@@ -292,24 +293,67 @@ class ShuffleBatcher:
         self.num_epochs = num_epochs
         self.rng = np.random.default_rng(seed)
         self.cap = max(1, min_after_dequeue)
-        self._src = self._source()
+        # the position in the epoch stream: the next example is row _index of
+        # pass _epoch (explicit counters, so that get_state can save them)
+        self._epoch, self._index = 0, 0
         self._buf: List[int] = []
         self._exhausted = False
 
-    def _source(self) -> Iterator[int]:
-        ep = 0
-        n = len(self.digits)
-        while n and (self.num_epochs is None or ep < self.num_epochs):
-            for i in range(n):
-                yield i
-            ep += 1
-
     def _fill(self):
-        while not self._exhausted and len(self._buf) < self.cap + self.batch_size:
-            try:
-                self._buf.append(next(self._src))
-            except StopIteration:
+        """Top the queue up to ``cap + batch_size`` rows of ``num_epochs``
+        passes in file order, a run of consecutive rows at a time."""
+        n = len(self.digits)
+        want = self.cap + self.batch_size - len(self._buf)
+        while want > 0 and not self._exhausted:
+            if not n or (self.num_epochs is not None and self._epoch >= self.num_epochs):
                 self._exhausted = True
+                break
+            take = min(want, n - self._index)
+            self._buf.extend(range(self._index, self._index + take))
+            self._index += take
+            want -= take
+            if self._index == n:
+                self._epoch, self._index = self._epoch + 1, 0
+
+    # ------------------------------------------------------------ state ----
+    def get_state(self) -> Dict[str, object]:
+        """Everything the next picks depend on: the PCG64 state (its 128-bit
+        integers as decimal strings: JSON has no such integers), the shuffle
+        buffer, the position in the epoch stream and whether it has run dry.
+        ``buf`` is an int64 array, the rest is JSON-serialisable."""
+        st = self.rng.bit_generator.state
+        return {"rng": {"bit_generator": st["bit_generator"],
+                        "state": str(st["state"]["state"]), "inc": str(st["state"]["inc"]),
+                        "has_uint32": int(st["has_uint32"]), "uinteger": int(st["uinteger"])},
+                "buf": np.asarray(self._buf, np.int64),
+                "epoch": int(self._epoch), "index": int(self._index),
+                "exhausted": bool(self._exhausted)}
+
+    def set_state(self, state) -> None:
+        """Continue from a ``get_state`` of a batcher over the same dataset,
+        batch size, epochs and queue size."""
+        r = state["rng"]
+        if r["bit_generator"] != self.rng.bit_generator.state["bit_generator"]:
+            raise ValueError("feed state of a %s generator, this batcher draws from %s" % (
+                r["bit_generator"], self.rng.bit_generator.state["bit_generator"]))
+        buf = [int(i) for i in np.asarray(state["buf"]).reshape(-1)]
+        n = len(self.digits)
+        if (buf and not (0 <= min(buf) and max(buf) < n)) or \
+                not 0 <= int(state["index"]) < max(n, 1):
+            raise ValueError("feed state points outside this dataset of %d examples" % n)
+        self.rng.bit_generator.state = {
+            "bit_generator": r["bit_generator"],
+            "state": {"state": int(r["state"]), "inc": int(r["inc"])},
+            "has_uint32": int(r["has_uint32"]), "uinteger": int(r["uinteger"])}
+        self._buf = buf
+        self._epoch, self._index = int(state["epoch"]), int(state["index"])
+        self._exhausted = bool(state["exhausted"])
+
+    def fingerprint(self) -> Dict[str, int]:
+        """What a saved feed state is only valid for: the dataset's length
+        and the CRC-32 of its digit counts."""
+        k = np.ascontiguousarray(self.digits, np.int32)
+        return {"examples": int(len(k)), "digits_crc32": int(zlib.crc32(k.tobytes()))}
 
     def next_indices(self) -> np.ndarray:
         """The dataset rows of the next batch (what ``next_batch`` gathers)."""
@@ -363,3 +407,12 @@ class DeviceFeed:
         k = torch.empty((len(idx),), dtype=torch.int32, device=self.device)
         self._ops.gather_rows(self.images, idx, x, ksrc=self.digits, kout=k)
         return x, k, self.batch_size
+
+    def get_state(self):
+        return self._picks.get_state()
+
+    def set_state(self, state) -> None:
+        self._picks.set_state(state)
+
+    def fingerprint(self):
+        return self._picks.fingerprint()

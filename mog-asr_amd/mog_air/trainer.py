@@ -10,9 +10,15 @@ IMAGE_SAVE_ITERATION iterations and at the end, the test model's
 reconstruction / misclassified / generation grids are written as PNG files
 under summary/ (``mog_air.visualize``).  TensorBoard event files are out of
 scope.
+
+Checkpoints: ``Saver`` writes the variables (models/air-model-<step>.npz),
+``StateSaver`` the full train state beside them (models/air-state-<step>.npz,
+``mog_air.checkpoint``); ``--restore`` continues a run from such a state
+(``restore``, ``LoopState``).
 """
 from __future__ import annotations
 
+import dataclasses
 import glob
 import logging
 import operator
@@ -23,7 +29,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import records
+from . import checkpoint, records
 from .evaluation import evaluation
 
 EPOCHS = 300
@@ -39,7 +45,8 @@ def add_common_args(parser, reader_threads: int):
     """The CLI flags shared by both entry points (training_air_original.py:49-60,
     train_air_pr.py:40-61) plus this framework's options (not in the
     reference): --iterations, --precision, --test-batch, --synth-per-count,
-    --write-synthetic, --device, --resident."""
+    --write-synthetic, --device, --resident, --save-every, --restore,
+    --restore-mode, --eval-only."""
     parser.add_argument("-r", "--results-folder", default="Not Valid")
     parser.add_argument("-k", "-key", "--key", default="")
     parser.add_argument("-gpu", "--gpu", default="-1")
@@ -64,6 +71,18 @@ def add_common_args(parser, reader_threads: int):
                              "(evaluation.DeviceEvaluator)")
     parser.add_argument("--no-images", action="store_true",
                         help="skip the PNG grids (training_air_original.py:368-411)")
+    parser.add_argument("--save-every", type=int, default=SAVE_PARAMS_EACH_ITERATIONS,
+                        help="iterations between two saves of models/air-model-<step>.npz (the "
+                             "variables) and models/air-state-<step>.npz (the full train state); "
+                             "0: only the state at the end")
+    parser.add_argument("--restore", default=None, metavar="PATH",
+                        help="an air-state-<step>.npz, or a models/ folder (its newest state)")
+    parser.add_argument("--restore-mode", choices=["resume", "weights"], default="resume",
+                        help="resume: continue the saved run; weights: its variables only "
+                             "(also from an air-model-<step>.npz), everything else fresh")
+    parser.add_argument("--eval-only", type=int, choices=[0, 1], default=0,
+                        help="1 (with --restore): the final test pass and grids of the restored "
+                             "state, no training")
 
 
 def select_gpu(gpu: str) -> None:
@@ -270,6 +289,65 @@ class Saver:
         return path
 
 
+@dataclasses.dataclass
+class LoopState:
+    """What the iteration loops carry from one iteration to the next beside
+    the models and the feed (saved with the train state, checkpoint.py).
+    ``rows`` (AIR): the [loss, accuracy, mse] of every iteration since the
+    last log line; ``logged`` (AIR-ASR): the log variables since then."""
+    step: int = 0
+    min_loss: float = 9999999.0
+    update_flag: bool = False
+    best: list = dataclasses.field(default_factory=lambda: [0.0, 0.0, 0.0, 0.0])
+    rows: list = dataclasses.field(default_factory=list)
+    logged: dict = dataclasses.field(default_factory=dict)
+
+    def as_dict(self) -> dict:
+        return {"step": int(self.step), "min_loss": float(self.min_loss),
+                "update_flag": bool(self.update_flag), "best": [float(v) for v in self.best],
+                "rows": [[float(v) for v in r] for r in self.rows],
+                "logged": {n: [float(x) for x in v] for n, v in self.logged.items()}}
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "LoopState":
+        return cls(**{f.name: d[f.name] for f in dataclasses.fields(cls)})
+
+
+class StateSaver:
+    """Saver's companion: models/air-state-<step>.npz, the newest 3 kept.
+    Every rank calls ``save`` (checkpoint.save_state gathers the per-rank
+    noise counters); rank 0 writes and rotates."""
+
+    def __init__(self, folder: str, train_model, test_model, feed, ctx):
+        self.folder, self.ctx = folder, ctx
+        self.models, self.feed = (train_model, test_model), feed
+
+    def save(self, loop: LoopState) -> None:
+        checkpoint.save_state(checkpoint.state_path(self.folder, loop.step), *self.models,
+                              feed=self.feed, loop=loop.as_dict(), ctx=self.ctx)
+        if self.ctx.main:
+            checkpoint.rotate(self.folder)
+
+
+def restore(args, train_model, test_model, feed, ctx, log) -> LoopState:
+    """--restore / --restore-mode / --eval-only: the loop state to start from
+    (a fresh one without --restore or with --restore-mode weights).  An
+    evaluation restores no feed, so it needs no dataset of the same
+    fingerprint."""
+    path = getattr(args, "restore", None)
+    eval_only = bool(getattr(args, "eval_only", 0))
+    if path is None:
+        if eval_only:
+            raise ValueError("--eval-only 1 needs --restore")
+        return LoopState()
+    path = checkpoint.resolve(path)
+    mode = getattr(args, "restore_mode", "resume")
+    saved = checkpoint.load_state(path, train_model, test_model,
+                                  feed=None if eval_only else feed, ctx=ctx, mode=mode)
+    log.info("Restored %s (%s) at step %d", path, mode, train_model.global_step)
+    return LoopState.from_dict(saved) if saved is not None else LoopState()
+
+
 def resident_ok(args, tr_x, test, test_model, log) -> bool:
     """--resident 1 is taken only when both datasets fit in half of the
     device's free memory and the test set is within the metrics kernel's caps
@@ -306,6 +384,16 @@ class _HostFeed:
         xg, kg = self.batcher.next_batch()
         x, k = self.ctx.shard(xg, kg)
         return x, k, len(kg)
+
+    # every rank runs the same shuffle and slices its shard: one state serves all
+    def get_state(self):
+        return self.batcher.get_state()
+
+    def set_state(self, state) -> None:
+        self.batcher.set_state(state)
+
+    def fingerprint(self):
+        return self.batcher.fingerprint()
 
 
 def make_feed(args, tr_x, tr_k, ctx, resident: bool):
@@ -371,21 +459,21 @@ def run_test(test_model, test, canvas: int, batch: int, evaluator=None):
 def train_loop(args, train_model, test_model, tr_x, tr_k, test, canvas, log, models_folder,
                extra_log=None, ctx: Optional[Dist] = None):
     """The iteration loop of training_air_original.py:226-503 (logging every
-    20, testing every 200, parameters every 10,000 iterations; the final
-    test when the input runs out)."""
+    20, testing every 200, parameters and the train state every --save-every
+    (10,000) iterations; the final test when the input runs out).  With
+    --restore the loop starts from the saved state; --eval-only 1 runs the
+    epilogue alone."""
     ctx = ctx or Dist()
     resident = resident_ok(args, tr_x, test, test_model, log)
     feed = make_feed(args, tr_x, tr_k, ctx, resident)
     test_dev, evaluator = (resident_test_set(args, test, canvas, test_model)
                            if resident and ctx.main else (None, None))
     saver = Saver(models_folder, "air-model")
-    min_loss, update_flag = 9999999.0, False
-    best = [0.0, 0.0, 0.0, 0.0]
-    hist = []
-    step = 0
+    states = StateSaver(models_folder, train_model, test_model, feed, ctx)
+    save_every = getattr(args, "save_every", SAVE_PARAMS_EACH_ITERATIONS)
+    st = restore(args, train_model, test_model, feed, ctx, log)
 
     def test_and_log(tag):
-        nonlocal update_flag
         if not ctx.main:
             ctx.barrier()
             return 0.0, 0.0, 0.0, 0.0
@@ -421,39 +509,47 @@ def train_loop(args, train_model, test_model, tr_x, tr_k, test, canvas, log, mod
 
     log.info("Training...\n")
     try:
-        while True:
-            if step % SAVE_PARAMS_EACH_ITERATIONS == 0 and ctx.main:
-                saver.save(train_model.params, step)
+        while not getattr(args, "eval_only", 0):
+            if save_every > 0 and st.step % save_every == 0:
+                if ctx.main:
+                    saver.save(train_model.params, st.step)
+                states.save(st)
             x, k, nglobal = feed.next_batch()
-            loss, acc, mse, step = train_model.step(x, k, global_batch=nglobal)
+            loss, acc, mse, st.step = train_model.step(x, k, global_batch=nglobal)
             if extra_log is not None:
-                extra_log(train_model, step)
-            hist.append([loss, acc, mse])
-            if step % LOG_EACH_ITERATION == 0:
-                l0, l1, l2 = ctx.mean(np.mean(hist[-LOG_EACH_ITERATION:], axis=0), args.device,
-                                      weight=len(k))
+                extra_log(train_model, st.step)
+            st.rows.append([loss, acc, mse])
+            if st.step % LOG_EACH_ITERATION == 0:
+                # (the rows since the last log line: the last LOG_EACH_ITERATION)
+                l0, l1, l2 = ctx.mean(np.mean(st.rows, axis=0), args.device, weight=len(k))
+                st.rows = []
                 log.info("iteration {}\ttrain loss {:.3f}\ttrain accuracy {:.2f}, "
-                         "train mse {:.3f}".format(step, l0, l1, l2))
-                if l0 < min_loss:
-                    update_flag, min_loss = True, l0
-            if step % TEST_EACH_ITERATION == 0:
-                tl, ta, tm, g_iou = test_and_log(step)
-                if update_flag:
-                    update_flag = False
-                    best = [tl, ta, tm, g_iou]
-                log.info("Current Best: elbo:{}\taccu:{}\tmse:{}\tiou:{}".format(*best))
-            if step % IMAGE_SAVE_ITERATION == 0:
-                save_images(step)
-            if args.iterations and step >= args.iterations:
+                         "train mse {:.3f}".format(st.step, l0, l1, l2))
+                if l0 < st.min_loss:
+                    st.update_flag, st.min_loss = True, l0
+            if st.step % TEST_EACH_ITERATION == 0:
+                tl, ta, tm, g_iou = test_and_log(st.step)
+                if st.update_flag:
+                    st.update_flag = False
+                    st.best = [tl, ta, tm, g_iou]
+                log.info("Current Best: elbo:{}\taccu:{}\tmse:{}\tiou:{}".format(*st.best))
+            if st.step % IMAGE_SAVE_ITERATION == 0:
+                save_images(st.step)
+            if args.iterations and st.step >= args.iterations:
                 raise StopIteration
+        raise StopIteration
     except StopIteration:
+        if not getattr(args, "eval_only", 0):
+            # before the final test, so that an evaluation of this file draws
+            # the noise the run's own final test drew
+            states.save(st)
         test_and_log("final")
         # the final reconstruction / misclassified grids are tagged 'final',
         # the final generation grids with the step (training_air_original.py:478-483)
-        save_images("final", gen_tag=step)
-        log.info("Final Best: elbo:{}\taccu:{}\tmse:{}\tiou:{}".format(*best))
+        save_images("final", gen_tag=st.step)
+        log.info("Final Best: elbo:{}\taccu:{}\tmse:{}\tiou:{}".format(*st.best))
         log.info("\ntraining has ended\n")
-    return step
+    return st.step
 
 
 TESET_EACH_ITERATION = 200  # (sic) train_air_pr.py:31
@@ -464,21 +560,20 @@ def train_loop_asr(args, train_model, test_model, tr_x, tr_k, test, canvas, log,
     """The iteration loop of train_air_pr.py:284-400: every step fetches the
     model's log variables; every 20 iterations their means are logged, every
     200 the test model runs on the test set (log variables + detection
-    metrics); parameters are saved every 10,000 iterations; the final test
-    when the input runs out.  Data parallel as train_loop."""
+    metrics); parameters and the train state are saved every --save-every
+    (10,000) iterations; the final test when the input runs out.  Data
+    parallel, --restore and --eval-only as train_loop."""
     ctx = ctx or Dist()
     resident = resident_ok(args, tr_x, test, test_model, log)
     feed = make_feed(args, tr_x, tr_k, ctx, resident)
     test_dev, evaluator = (resident_test_set(args, test, canvas, test_model)
                            if resident and ctx.main else (None, None))
     saver = Saver(models_folder, "air-model")
-    min_loss, update_flag = 9999999.0, False
-    best = [0.0, 0.0, 0.0, 0.0]
-    logged = {}
-    step = 0
+    states = StateSaver(models_folder, train_model, test_model, feed, ctx)
+    save_every = getattr(args, "save_every", SAVE_PARAMS_EACH_ITERATIONS)
+    st = restore(args, train_model, test_model, feed, ctx, log)
 
     def test_and_log(tag):
-        nonlocal update_flag
         if not ctx.main:
             ctx.barrier()
             return
@@ -493,12 +588,12 @@ def train_loop_asr(args, train_model, test_model, tr_x, tr_k, test, canvas, log,
         log.info("test:{:6d}\tprecision:{}\trecall:{}\tgtIoU:{:.4f}\tdetectionIoU:{:.4f}"
                  "\tglobal_iou:{:.4f}".format(tag, p, r, gt_iou, det_iou, g_iou))
         lv = test_model.log_variables
-        if update_flag:
-            update_flag = False
-            best[:] = [lv["elbo"], lv["accu"], lv["mse"], g_iou]
+        if st.update_flag:
+            st.update_flag = False
+            st.best = [lv["elbo"], lv["accu"], lv["mse"], g_iou]
         log.info("test:{:6d}\t".format(tag) +
                  "".join("{}:{:.4f}\t".format(n, v) for n, v in lv.items()))
-        log.info("Current Best: elbo:{}\taccu:{}\tmse:{}\tiou:{}".format(*best))
+        log.info("Current Best: elbo:{}\taccu:{}\tmse:{}\tiou:{}".format(*st.best))
 
     summary_folder = os.path.join(os.path.dirname(os.path.normpath(models_folder)), "summary")
     vis_n = args.test_batch if getattr(args, "test_batch", 0) > 0 else len(test[1])
@@ -514,34 +609,42 @@ def train_loop_asr(args, train_model, test_model, tr_x, tr_k, test, canvas, log,
 
     log.info("Training...\n")
     try:
-        while True:
-            if step % SAVE_PARAMS_EACH_ITERATIONS == 0 and ctx.main:
-                saver.save(train_model.params, step)
+        while not getattr(args, "eval_only", 0):
+            if save_every > 0 and st.step % save_every == 0:
+                if ctx.main:
+                    saver.save(train_model.params, st.step)
+                states.save(st)
             x, k, nglobal = feed.next_batch()
-            _, _, _, step = train_model.step(x, k, global_batch=nglobal)
-            for n, v in train_model.log_variables.items():
-                logged.setdefault(n, []).append(v)
-            if step % LOG_EACH_ITERATION == 0:
-                line = "step:{:6d}\t".format(step)
-                # the global batch's means (shard-size weighted over ranks)
-                means = ctx.mean([np.mean(v) for v in logged.values()], args.device,
+            _, _, _, st.step = train_model.step(x, k, global_batch=nglobal)
+            lv = train_model.log_variables
+            for n, v in lv.items():
+                st.logged.setdefault(n, []).append(v)
+            if st.step % LOG_EACH_ITERATION == 0:
+                line = "step:{:6d}\t".format(st.step)
+                # the global batch's means (shard-size weighted over ranks), in
+                # the model's order (a restored ``logged`` may list them in another)
+                means = ctx.mean([np.mean(st.logged[n]) for n in lv], args.device,
                                  weight=len(k))
-                for n, v in zip(logged, means):
-                    if n == "TotLoss" and v < min_loss:
-                        min_loss, update_flag = float(v), True
+                for n, v in zip(lv, means):
+                    if n == "TotLoss" and v < st.min_loss:
+                        st.min_loss, st.update_flag = float(v), True
                     line += "{}:{:.4f}\t".format(n, v)
                 log.info(line)
-                logged = {}
-            if step % TESET_EACH_ITERATION == 0:
-                test_and_log(step)
-            if step % IMAGE_SAVE_ITERATION == 0:
-                save_images(step)
-            if args.iterations and step >= args.iterations:
+                st.logged = {}
+            if st.step % TESET_EACH_ITERATION == 0:
+                test_and_log(st.step)
+            if st.step % IMAGE_SAVE_ITERATION == 0:
+                save_images(st.step)
+            if args.iterations and st.step >= args.iterations:
                 raise StopIteration
+        raise StopIteration
     except StopIteration:
-        test_and_log(step)  # the reference logs the step here too (train_air_pr.py:426-430)
+        if not getattr(args, "eval_only", 0):
+            states.save(st)  # before the final test (see train_loop)
+        # the reference logs the step here too (train_air_pr.py:426-430)
+        test_and_log(st.step)
         # the final generation grids are tagged with the step (train_air_pr.py:462-469)
-        save_images("final", gen_tag=step)
-        log.info("Final Best: elbo:{}\taccu:{}\tmse:{}\tiou:{}".format(*best))
+        save_images("final", gen_tag=st.step)
+        log.info("Final Best: elbo:{}\taccu:{}\tmse:{}\tiou:{}".format(*st.best))
         log.info("\ntraining has ended\n")
-    return step
+    return st.step

@@ -6,6 +6,8 @@ running the ASR model (mog_air.asr_model.AIRModel, the reference's
 air/air_number_bbox_location.py) on MI355X.
 
     python train_air_pr.py -dn 13 -ds 20k -gm 100 -gne 10 [--iterations N]
+                           [--save-every N] [--restore PATH [--restore-mode weights]
+                                             [--eval-only 1]]
 
 Model configuration: train_air_pr.py:160-213 (max_steps 6, LSTM 256, VAE
 784-512-256-50 with likelihood std 0, fixed scale prior (learned with

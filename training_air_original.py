@@ -5,6 +5,8 @@ lines, running the AIR train step on MI355X through mog_air.AIRModel.
 
     python training_air_original.py -dn 13 -ds 20k [--iterations N] [--precision bf16]
                                     [--cnn 1 [--cnn_filters 8]]
+                                    [--save-every N] [--restore PATH [--restore-mode weights]
+                                                      [--eval-only 1]]
 
 Model configuration: training_air_original.py:158-211 (max_steps 6, LSTM 256,
 VAE 784-512-256-50, scale prior -1 / 0.05, lr 1e-4, clip 1.0, z_pres prior
