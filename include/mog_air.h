@@ -412,12 +412,10 @@ int mog_gemm_bf16(int batch, const void* const* A, const void* const* B, void* c
                   float* const* colsum, int M, int N, int K, int lda, int ldb, int ldc,
                   int ldaux, int tn, int epi, int out_bf16, float aux_scale, int splitk,
                   void* stream);
-/* fp32 -> bf16 weight packing: dst[r][c] = src[c][r] (transpose) or src[r][c],
- * zero outside the (src_rows, src_cols) source extent. */
-int mog_cvt_bf16(const float* src, int src_rows, int src_cols, int ld_src, void* dst, int rows,
-                 int cols, int ld_dst, int transpose, void* stream);
-/* Up to 16 of the above in one launch; dims[7*j ..] = src_rows, src_cols,
- * ld_src, rows, cols, ld_dst, transpose of job j.  transpose == 2 packs W^T
+/* fp32 -> bf16 weight packing, up to 16 matrices in one launch: dst[r][c] =
+ * src[c][r] (transpose) or src[r][c], zero outside the (src_rows, src_cols)
+ * source extent; dims[7*j ..] = src_rows, src_cols, ld_src, rows, cols,
+ * ld_dst, transpose of job j.  transpose == 2 packs W^T
  * (W = src [src_rows = in][src_cols = out]) in MFMA B-fragment order for
  * mog_stn_vae_step_forward: rows = out padded to 16, cols = in padded to 32,
  * element ((ct*(cols/32) + ks)*64 + lane)*8 + q = W[ks*32 + 8*(lane/16) + q]
@@ -440,8 +438,6 @@ int mog_recon_loss(const float* x, float* canvas, const float* parts, int nparts
 /* out[k] = mean_b a_k[b] for the non-NULL a_k (k < 4). */
 int mog_batch_mean(const float* a0, const float* a1, const float* a2, const float* a3, int B,
                    float* out, void* stream);
-/* out[n] += sum_r X[r*ld + n]  (BiasAddGrad) */
-int mog_colsum_add(const float* X, int R, int N, int ld, float* out, void* stream);
 /* Weight and bias gradients of the heads' 1- / 2-column output layers
  * (air_model.py:462-499 backward): gw[z] [HS, k[z]] += hid[z]^T dout[z],
  * gb[z] [k[z]] += column sums of dout[z] (gb may be NULL), over R rows; hid[z]
@@ -517,7 +513,7 @@ int mog_generation_prior(int G, int Z, float s_pm, float s_plv, float h_pm, floa
  * gsm0 gsm1 gslv0 gslv1 plo lo y z act_old act live zkl skl shkl prn zprob
  * gcm gclv (zkl / skl / shkl masked as the reference's tf.where, prn
  * live-gated; slots 28 / 29, the learned scale prior's mean and log-variance,
- * are written and read by the *_learned entry points only).
+ * are written and read with gw only).
  * w[20] (TF [in,out] layout): inf_shift dense_1 W,b, dense_3 W,b; inf_scale
  * dense W,b [258,64], dense_1 W,b [66,1], dense_2 W,b, dense_3 W,b; gen_shift
  * dense_1 W,b, dense_3 W,b; z_pres prior dense_1 W,b; z_pres log-odds
@@ -526,12 +522,13 @@ int mog_generation_prior(int G, int Z, float s_pm, float s_plv, float h_pm, floa
  * inf_scale m / v chains over h (finished in place: + shift latent terms,
  * bias, relu).  gammas[8] = num, margin, element, bbox, size, area, area_min,
  * area_max.  T <= 8 steps, <= 8 allowed counts.
- * Learned scale prior (fix_scale_distribution=False, :482-509, :729-746; the
- * *_learned entry points): gw[8] = gen_scale dense W,b [258,64], dense_1 W,b
- * [66,1], dense_2 W,b, dense_3 W,b; hid / dpre have 10 entries, 8 / 9 the
- * gen_scale m / v chains over hg (finished in place like 6 / 7); the scale KL
- * is taken against N(gcm, exp(gclv)) from those heads per image instead of
- * the constant scale_prior_*; douts has 14 columns (+ d gcm, d gclv). */
+ * Learned scale prior (fix_scale_distribution=False, :482-509, :729-746): gw
+ * non-NULL, gw[8] = gen_scale dense W,b [258,64], dense_1 W,b [66,1], dense_2
+ * W,b, dense_3 W,b (gw == NULL: the fixed prior N(scale_prior_mean,
+ * scale_prior_var)); hid / dpre then have 10 entries, 8 / 9 the gen_scale
+ * m / v chains over hg (finished in place like 6 / 7); the scale KL is taken
+ * against N(gcm, exp(gclv)) from those heads per image and the constant
+ * scale_prior_* are not read; douts has 14 columns (+ d gcm, d gclv). */
 /* U rows [z (Z) | ss (3) | h (H) | 0] of the two LSTMCell inputs (:403-412,
  * :457-463); null sources read as zeros.  out2 != NULL: the second cell's rows
  * [z | ss | h2 | 0] into out2 in the same launch. */
@@ -552,19 +549,12 @@ int mog_asr_unpack_parts(int B, int Z, int H, int ld, const float* dU, const flo
  * live flag of one step (:414-772) */
 int mog_asr_step_forward(int B, int step, int train, int fix_steps, float thr, float temperature,
                          float scale_prior_mean, float scale_prior_var, float scale_prior_logvar,
-                         float gamma_num, const float* const* w, float* const* hid,
-                         const float* eps_shift, const float* eps_scale, const float* u,
-                         float* stop, int* digits, int* live, float* rec, float* theta_fwd,
-                         float* theta_back, float* ss, float* scale, float* shift, float* zprob,
-                         float* zmask, float* zval, float* zc, void* stream);
-int mog_asr_step_forward_learned(int B, int step, int train, int fix_steps, float thr,
-                                 float temperature, float gamma_num, const float* const* w,
-                                 const float* const* gw, float* const* hid,
-                                 const float* eps_shift, const float* eps_scale, const float* u,
-                                 float* stop, int* digits, int* live, float* rec,
-                                 float* theta_fwd, float* theta_back, float* ss, float* scale,
-                                 float* shift, float* zprob, float* zmask, float* zval, float* zc,
-                                 void* stream);
+                         float gamma_num, const float* const* w, const float* const* gw,
+                         float* const* hid, const float* eps_shift, const float* eps_scale,
+                         const float* u, float* stop, int* digits, int* live, float* rec,
+                         float* theta_fwd, float* theta_back, float* ss, float* scale,
+                         float* shift, float* zprob, float* zmask, float* zval, float* zc,
+                         void* stream);
 /* per image KL sums (klsum, the reconstruction kernel's runloss), pr_loss
  * and its area / out / size / overlap terms over the executed steps; zsum[t]
  * = sum_b z_pres_prob (to be all-reduced over ranks for the margin loss)
@@ -583,24 +573,17 @@ int mog_asr_terms_backward(int B, int T, int C, int nc, const int* cons, const f
                            float grad_scale, float inv_batch_global, const float* rec,
                            const int* live, const float* zsum, float* dreg, void* stream);
 /* one step's backward of mog_asr_step_forward: douts [B][12] = d(sm0 sm1 slv0
- * slv1 lo gsm0 gsm1 gslv0 gslv1 plo cm clv), dpre[8] [B,64] hidden-layer
- * pre-activation gradients; dss [B,3] = gradient reaching this step's latents
- * from the next step's LSTM inputs (or null) */
+ * slv1 lo gsm0 gsm1 gslv0 gslv1 plo cm clv) ([B][14] with gw: + gcm gclv),
+ * dpre[8] (dpre[10] with gw) [B,64] hidden-layer pre-activation gradients;
+ * dss [B,3] = gradient reaching this step's latents from the next step's LSTM
+ * inputs (or null) */
 int mog_asr_step_backward(int B, int train, int fix_steps, float temperature,
                           float scale_prior_mean, float scale_prior_var, float grad_scale,
-                          const float* const* w, float* const* hid, const float* rec,
-                          const float* eps_shift, const float* eps_scale, const float* dtheta_fwd,
-                          const float* dtheta_back, const float* dot, const float* dreg,
-                          const float* dss, float* douts, float* const* dpre, void* stream);
-/* the same for mog_asr_step_forward_learned: douts [B][14] (+ gcm gclv),
- * dpre[10] */
-int mog_asr_step_backward_learned(int B, int train, int fix_steps, float temperature,
-                                  float grad_scale, const float* const* w,
-                                  const float* const* gw, float* const* hid, const float* rec,
-                                  const float* eps_shift, const float* eps_scale,
-                                  const float* dtheta_fwd, const float* dtheta_back,
-                                  const float* dot, const float* dreg, const float* dss,
-                                  float* douts, float* const* dpre, void* stream);
+                          const float* const* w, const float* const* gw, float* const* hid,
+                          const float* rec, const float* eps_shift, const float* eps_scale,
+                          const float* dtheta_fwd, const float* dtheta_back, const float* dot,
+                          const float* dreg, const float* dss, float* douts, float* const* dpre,
+                          void* stream);
 
 /* ---- AIR-ASR generation (air_number_bbox_location.py:1124-1361) ----------
  * One step of the generation loop for G images, after the generative
@@ -615,27 +598,21 @@ int mog_asr_step_backward_learned(int B, int train, int fix_steps, float tempera
  * (:1203-1205); prior log-odds +-100 by step < fix_steps, or the learned
  * chain; zval = rint(sigmoid((lo + logistic(u)) / temperature)); stop += 1 -
  * zval; zmask = stop < thr; digits += zmask; live[step + 1] = 1 if any image
- * is still counting (live [T+1], as mog_asr_step_forward). */
+ * is still counting (live [T+1], as mog_asr_step_forward).
+ * Learned scale prior (:1170-1201): gw non-NULL (gw[8] as
+ * mog_asr_step_forward) and ghid[2] [G,64] = the gen_scale dense / dense_2
+ * chains over the new output hg (raw: a GEMM from +0 without bias).  The
+ * kernel adds the generated shift latent's two terms, bias and relu, runs the
+ * 66-term output chains, and draws scale latent = gcm + eps_scale
+ * sqrt(exp(gclv)); scale_prior_* are not read.  gw == NULL: ghid unused. */
 int mog_asr_gen_step(int G, int Z, int step, int fix_steps, float thr, float temperature,
                      float scale_prior_mean, float scale_prior_var, float s,
                      float vae_prior_mean, float vae_prior_logvar, const float* const* w,
-                     const float* const* hid, const float* eps_shift, const float* eps_scale,
+                     const float* const* hid, const float* const* gw,
+                     const float* const* ghid, const float* eps_shift, const float* eps_scale,
                      const float* eps_z, const float* u, float* stop, int* digits, int* live,
                      float* ss, float* z, float* theta_back, float* zval, float* zmask,
                      void* stream);
-/* The same with the learned scale prior (:1170-1201): ghid[2] [G,64] = the
- * gen_scale dense / dense_2 chains over the new output hg (raw: a GEMM from
- * +0 without bias), gw[8] as mog_asr_step_forward_learned.  The kernel adds
- * the generated shift latent's two terms, bias and relu, runs the 66-term
- * output chains, and draws scale latent = gcm + eps_scale sqrt(exp(gclv)). */
-int mog_asr_gen_step_learned(int G, int Z, int step, int fix_steps, float thr, float temperature,
-                             float s, float vae_prior_mean, float vae_prior_logvar,
-                             const float* const* w, const float* const* hid,
-                             const float* const* gw, const float* const* ghid,
-                             const float* eps_shift, const float* eps_scale, const float* eps_z,
-                             const float* u, float* stop, int* digits, int* live, float* ss,
-                             float* z, float* theta_back, float* zval, float* zmask,
-                             void* stream);
 /* out[i] = x[i] > u[i] ? 1 : 0 for n floats: the Bernoulli sample of the
  * decoded window (vae.py:83-84 relu(sign(samples - U))).  16-byte vector
  * accesses when x, u and out are 16-byte aligned; out may be x or u. */

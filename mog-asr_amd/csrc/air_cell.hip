@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "mog_common.h"
+#include "step_math.h"
 
 namespace {
 
@@ -159,54 +160,6 @@ struct HeadPtrs {
   const float* b2[5];   // [k]
 };
 
-// sum_k a[k] w[k ldw] as ONE fma chain in k order (the oracle's dense()).
-// The operands of 32 k-steps are loaded before their fmas: a rolled
-// load-then-fma loop paid one memory round trip per k (16 us per launch at
-// the reference's batch of 64, where the step kernel is one or two
-// workgroups); same fma sequence, same bits.
-__device__ __forceinline__ float chain_dot(const float* a, const float* w, int K, int ldw) {
-#pragma clang fp contract(off)
-  constexpr int KB = 32;
-  float acc = 0.0f;
-  int k = 0;
-  for (; k + KB <= K; k += KB) {
-    float av[KB], wv[KB];
-#pragma unroll
-    for (int i = 0; i < KB; ++i) {
-      av[i] = a[k + i];
-      wv[i] = w[(size_t)(k + i) * ldw];
-    }
-#pragma unroll
-    for (int i = 0; i < KB; ++i) acc = fmaf(av[i], wv[i], acc);
-  }
-  for (; k < K; ++k) acc = fmaf(a[k], w[(size_t)k * ldw], acc);
-  return acc;
-}
-
-__device__ __forceinline__ float lse0(float a) {
-#pragma clang fp contract(off)
-  float m = a > 0.0f ? a : 0.0f;
-  if (!(m - m == 0.0f)) m = 0.0f;
-  return mog_logf(mog_expf(0.0f - m) + mog_expf(a - m)) + m;
-}
-
-__device__ __forceinline__ float concrete_kl(float y, float plo, float pT, float qlo, float qT) {
-#pragma clang fp contract(off)
-  const float eps = 1e-9f;
-  const float lse_p = lse0(-y * pT + plo);
-  const float log_prior = ((mog_logf(pT + eps) - y * (pT + 1.0f)) + plo) - 2.0f * lse_p;
-  const float lse_q = lse0(-y * qT + qlo);
-  const float log_post = ((mog_logf(qT + eps) - y * (qT + 1.0f)) + qlo) - 2.0f * lse_q;
-  return log_post - log_prior;
-}
-
-__device__ __forceinline__ float gauss_kl_term(float plv, float lv, float var, float pv,
-                                               float mean, float pm) {
-#pragma clang fp contract(off)
-  const float d = mean - pm;
-  return (((plv - lv) - 1.0f) + var / pv) + (d * d) / pv;
-}
-
 struct StepFwdIO {
   const float* eps_scale;  // [B]
   const float* eps_shift;  // [B,2]
@@ -228,6 +181,76 @@ struct StepFwdIO {
   float* zval;             // [B] z_pres value (canvas coefficient)
   float* zc;               // [B] active ? z : 0 (STN-write backward scale; may be null)
 };
+
+// the seven head outputs of one (step, image): scale mean / log-variance,
+// shift means, shift log-variances, z_pres log-odds
+struct HeadOut {
+  float sm, slv, hm0, hm1, hv0, hv1, lo;
+};
+
+// what a step computes from its head outputs and its noise alone, whatever
+// the loop state is
+struct StepVals {
+  float s, tx, ty, svar, hvar0, hvar1, y, z, zkl, kl_end, skl, shkl;
+};
+
+// The state-free part of one AIR step, shared by step_fwd_kernel and
+// step_fwd_steps_kernel (prior_bias: the step's z_pres prior offset).  No
+// store here: the callers load every input before their first store.
+__device__ __forceinline__ StepVals step_values(const StepCfg& cfg, float prior_bias,
+                                                const HeadOut& h, float e_s, float e_h0,
+                                                float e_h1, float uu) {
+#pragma clang fp contract(off)
+  StepVals v;
+  // scale / shift sampling (air_model.py:471-477, :492-498; :186-192)
+  v.svar = mog_expf(h.slv);
+  v.s = mog_sigmoidf(h.sm + e_s * sqrtf(v.svar));
+  v.hvar0 = mog_expf(h.hv0);
+  v.hvar1 = mog_expf(h.hv1);
+  v.tx = mog_tanhf(h.hm0 + e_h0 * sqrtf(v.hvar0));
+  v.ty = mog_tanhf(h.hm1 + e_h1 * sqrtf(v.hvar1));
+  // z_pres (air_model.py:590-620, concrete.py:20-27)
+  v.y = (h.lo + logistic_noise(uu)) / cfg.temperature;
+  v.z = mog_sigmoidf(v.y);
+  if (!cfg.train) v.z = rintf(v.z);
+  // z_pres KLs: against the prior, and against the end-of-count prior (:622-653)
+  v.kl_end = 0.0f;
+  if (cfg.use_num_prior)
+    v.kl_end = concrete_kl(v.y, -100.0f, cfg.temperature, h.lo, cfg.temperature);
+  v.zkl = concrete_kl(v.y, prior_log_odds(cfg) + prior_bias, cfg.temperature, h.lo,
+                      cfg.temperature);
+  // scale & shift KLs (:677-705)
+  v.skl = 0.5f * gauss_kl_term(cfg.s_plv, h.slv, v.svar, cfg.s_pv, h.sm, cfg.s_pm);
+  const float shs = gauss_kl_term(cfg.h_plv, h.hv0, v.hvar0, cfg.h_pv, h.hm0, cfg.h_pm) +
+                    gauss_kl_term(cfg.h_plv, h.hv1, v.hvar1, cfg.h_pv, h.hm1, cfg.h_pm);
+  v.shkl = 0.5f * shs;
+  return v;
+}
+
+// Stores what depends on those values alone: theta / theta^-1 (:500-577),
+// scale, shift, z_pres probability and the three KL outputs to row rb, record
+// slots R_SM .. R_Z to column b of r (the step's records [R_NREC, B]).
+__device__ __forceinline__ void step_values_store(const StepFwdIO& io, long rb, float* r, int B,
+                                                  int b, const HeadOut& h, const StepVals& v) {
+#pragma clang fp contract(off)
+  float* tf = io.theta_fwd + rb * 6;
+  tf[0] = v.s; tf[1] = 0.0f; tf[2] = v.tx; tf[3] = 0.0f; tf[4] = v.s; tf[5] = v.ty;
+  const float is = 1.0f / v.s;
+  float* tb = io.theta_back + rb * 6;
+  tb[0] = is; tb[1] = 0.0f; tb[2] = -v.tx / v.s; tb[3] = 0.0f; tb[4] = is; tb[5] = -v.ty / v.s;
+  io.scale_out[rb] = v.s;
+  io.shift_out[2 * rb] = v.tx;
+  io.shift_out[2 * rb + 1] = v.ty;
+  io.zprob_out[rb] = mog_sigmoidf(h.lo);
+  io.zkl_out[rb] = v.zkl;
+  io.skl_out[rb] = v.skl;
+  io.shkl_out[rb] = v.shkl;
+  r[R_SM * B + b] = h.sm; r[R_SLV * B + b] = h.slv;
+  r[R_HM0 * B + b] = h.hm0; r[R_HM1 * B + b] = h.hm1;
+  r[R_HLV0 * B + b] = h.hv0; r[R_HLV1 * B + b] = h.hv1;
+  r[R_LO * B + b] = h.lo; r[R_S * B + b] = v.s; r[R_TX * B + b] = v.tx; r[R_TY * B + b] = v.ty;
+  r[R_Y * B + b] = v.y; r[R_Z * B + b] = v.z;
+}
 
 // 8 lanes per image: lanes 0..6 each evaluate one head-output fma chain
 // (scale-mean, scale-logvar, shift-mean x/y, shift-logvar x/y, z_pres
@@ -260,88 +283,47 @@ __global__ __launch_bounds__(256) void step_fwd_kernel(StepCfg cfg, HeadPtrs hp,
     const int K = head == 4 ? HZ : HS;
     v = chain_dot(hp.hid[head] + (size_t)b * K, hp.w2[head] + col, K, kw) + hp.b2[head][col];
   }
-  const float sm = __shfl(v, 0, 8), slv = __shfl(v, 1, 8);
-  const float hm0 = __shfl(v, 2, 8), hm1 = __shfl(v, 3, 8);
-  const float hv0 = __shfl(v, 4, 8), hv1 = __shfl(v, 5, 8);
-  const float lo = __shfl(v, 6, 8);
+  const HeadOut h{__shfl(v, 0, 8), __shfl(v, 1, 8), __shfl(v, 2, 8), __shfl(v, 3, 8),
+                  __shfl(v, 4, 8), __shfl(v, 5, 8), __shfl(v, 6, 8)};
   if (b >= B || j != 0) return;
-
-  // scale / shift sampling (air_model.py:471-477, :492-498; :186-192)
-  const float svar = mog_expf(slv);
-  const float s = mog_sigmoidf(sm + e_s * sqrtf(svar));
-  const float hvar0 = mog_expf(hv0), hvar1 = mog_expf(hv1);
-  const float tx = mog_tanhf(hm0 + e_h0 * sqrtf(hvar0));
-  const float ty = mog_tanhf(hm1 + e_h1 * sqrtf(hvar1));
-  float* tf = io.theta_fwd + (size_t)b * 6;
-  tf[0] = s; tf[1] = 0.0f; tf[2] = tx; tf[3] = 0.0f; tf[4] = s; tf[5] = ty;
-  const float is = 1.0f / s;
-  float* tb = io.theta_back + (size_t)b * 6;
-  tb[0] = is; tb[1] = 0.0f; tb[2] = -tx / s; tb[3] = 0.0f; tb[4] = is; tb[5] = -ty / s;
-  io.scale_out[b] = s;
-  io.shift_out[2 * b] = tx;
-  io.shift_out[2 * b + 1] = ty;
-
-  // z_pres (air_model.py:590-620, concrete.py:20-27)
-  const float eps = 1e-9f;
-  const float noise = mog_logf(uu + eps) - mog_logf((1.0f - uu) + eps);
-  const float y = (lo + noise) / cfg.temperature;
-  float z = mog_sigmoidf(y);
-  if (!cfg.train) z = rintf(z);
-  io.zprob_out[b] = mog_sigmoidf(lo);
+  const StepVals sv = step_values(cfg, cfg.prior_bias, h, e_s, e_h0, e_h1, uu);
 
   // z_pres KL with the OLD stopping sum (:622-653)
-  float kl_end = 0.0f;
-  if (cfg.use_num_prior) kl_end = concrete_kl(y, -100.0f, cfg.temperature, lo, cfg.temperature);
-  const float zkl = concrete_kl(y, prior_log_odds(cfg) + cfg.prior_bias, cfg.temperature, lo,
-                                cfg.temperature);
   const bool act_old = stop_old < cfg.thr;
   float rl = rl0;
   // the z_pres term this step adds (recorded: mog_air_runloss replays the sum)
-  const float zterm = live ? (act_old ? zkl : kl_end) : 0.0f;
+  const float zterm = live ? (act_old ? sv.zkl : sv.kl_end) : 0.0f;
   if (live) rl = rl + zterm;
-  io.zkl_out[b] = zkl;
-
   // stopping sum, digit count, live flag for the next step (:428-432, :659-663)
-  const float stop_new = stop_old + (1.0f - z);
-  io.stop[b] = stop_new;
+  const float stop_new = stop_old + (1.0f - sv.z);
   const bool act = stop_new < cfg.thr;
+  // scale & shift KLs with the NEW stopping sum (:677-705)
+  if (act) rl = rl + sv.skl;
+  if (act) rl = rl + sv.shkl;
+
+  step_values_store(io, b, io.rec, B, b, h, sv);
+  io.stop[b] = stop_new;
   if (act) {
     io.digits[b] = dig + 1;
     io.live[cfg.step + 1] = 1;
   }
-
-  // scale & shift KLs with the NEW stopping sum (:677-705)
-  const float skl = 0.5f * gauss_kl_term(cfg.s_plv, slv, svar, cfg.s_pv, sm, cfg.s_pm);
-  if (act) rl = rl + skl;
-  const float shs = gauss_kl_term(cfg.h_plv, hv0, hvar0, cfg.h_pv, hm0, cfg.h_pm) +
-                    gauss_kl_term(cfg.h_plv, hv1, hvar1, cfg.h_pv, hm1, cfg.h_pm);
-  const float shkl = 0.5f * shs;
-  if (act) rl = rl + shkl;
   io.runloss[b] = rl;
-  io.skl_out[b] = skl;
-  io.shkl_out[b] = shkl;
   io.zmask[b] = act ? 1.0f : 0.0f;
-  io.zval[b] = z;
-
+  io.zval[b] = sv.z;
   float* r = io.rec;
-  r[R_SM * B + b] = sm; r[R_SLV * B + b] = slv;
-  r[R_HM0 * B + b] = hm0; r[R_HM1 * B + b] = hm1;
-  r[R_HLV0 * B + b] = hv0; r[R_HLV1 * B + b] = hv1;
-  r[R_LO * B + b] = lo; r[R_S * B + b] = s; r[R_TX * B + b] = tx; r[R_TY * B + b] = ty;
-  r[R_Y * B + b] = y; r[R_Z * B + b] = z;
   r[R_ACT_OLD * B + b] = act_old ? 1.0f : 0.0f;
   r[R_ACT * B + b] = act ? 1.0f : 0.0f;
   r[R_LIVE * B + b] = live ? 1.0f : 0.0f;
-  r[R_ZC * B + b] = act ? z : 0.0f;
+  r[R_ZC * B + b] = act ? sv.z : 0.0f;
   r[R_ZTERM * B + b] = zterm;
-  if (io.zc) io.zc[b] = act ? z : 0.0f;
+  if (io.zc) io.zc[b] = act ? sv.z : 0.0f;
 }
 
 // Every loop step of the batch in ONE launch (AIR: the heads read h_t only --
 // the step's VAE never feeds the recurrence -- so once the LSTM chain has run,
 // every step's head outputs are available and only the per-image loop state
 // is sequential).  Operands of step t at step-0 pointer + t * (B * width);
-// the step values are the ones step_fwd_kernel computes, in the same order.
+// the step values are step_fwd_kernel's (step_values, step_values_store).
 // What depends on the batch-wide loop predicate is NOT resolved here: live[t]
 // is known only once every image of step t - 1 (and every rank, under data
 // parallelism) has run, so rec[R_ZTERM] holds the z_pres term the step adds
@@ -387,58 +369,21 @@ __global__ __launch_bounds__(256) void step_fwd_steps_kernel(StepCfg cfg, HeadPt
     v = chain_dot(hp.hid[head] + tc * q.hid_step + (size_t)bc * K, hp.w2[head] + col, K, kw) +
         hp.b2[head][col];
   }
-  const float sm = __shfl(v, g0, LPI), slv = __shfl(v, g0 + 1, LPI);
-  const float hm0 = __shfl(v, g0 + 2, LPI), hm1 = __shfl(v, g0 + 3, LPI);
-  const float hv0 = __shfl(v, g0 + 4, LPI), hv1 = __shfl(v, g0 + 5, LPI);
-  const float lo = __shfl(v, g0 + 6, LPI);
-
-  // the step's state-free values, as step_fwd_kernel computes them
-  const float svar = mog_expf(slv);
-  const float s = mog_sigmoidf(sm + e_s * sqrtf(svar));
-  const float hvar0 = mog_expf(hv0), hvar1 = mog_expf(hv1);
-  const float tx = mog_tanhf(hm0 + e_h0 * sqrtf(hvar0));
-  const float ty = mog_tanhf(hm1 + e_h1 * sqrtf(hvar1));
-  const float eps = 1e-9f;
-  const float noise = mog_logf(uu + eps) - mog_logf((1.0f - uu) + eps);
-  const float y = (lo + noise) / cfg.temperature;
-  float z = mog_sigmoidf(y);
-  if (!cfg.train) z = rintf(z);
-  float kl_end = 0.0f;
-  if (cfg.use_num_prior) kl_end = concrete_kl(y, -100.0f, cfg.temperature, lo, cfg.temperature);
-  const float zkl = concrete_kl(y, prior_log_odds(cfg) + pbias, cfg.temperature, lo,
-                                cfg.temperature);
-  const float skl = 0.5f * gauss_kl_term(cfg.s_plv, slv, svar, cfg.s_pv, sm, cfg.s_pm);
-  const float shs = gauss_kl_term(cfg.h_plv, hv0, hvar0, cfg.h_pv, hm0, cfg.h_pm) +
-                    gauss_kl_term(cfg.h_plv, hv1, hvar1, cfg.h_pv, hm1, cfg.h_pm);
-  const float shkl = 0.5f * shs;
-  if (b < B && t < T && j == 0) {
-    float* tf = io.theta_fwd + rb * 6;
-    tf[0] = s; tf[1] = 0.0f; tf[2] = tx; tf[3] = 0.0f; tf[4] = s; tf[5] = ty;
-    const float is = 1.0f / s;
-    float* tb = io.theta_back + rb * 6;
-    tb[0] = is; tb[1] = 0.0f; tb[2] = -tx / s; tb[3] = 0.0f; tb[4] = is; tb[5] = -ty / s;
-    io.scale_out[rb] = s;
-    io.shift_out[2 * rb] = tx;
-    io.shift_out[2 * rb + 1] = ty;
-    io.zprob_out[rb] = mog_sigmoidf(lo);
-    io.zkl_out[rb] = zkl;
-    io.skl_out[rb] = skl;
-    io.shkl_out[rb] = shkl;
-    float* r = io.rec + (size_t)tc * R_NREC * B;
-    r[R_SM * B + bc] = sm; r[R_SLV * B + bc] = slv;
-    r[R_HM0 * B + bc] = hm0; r[R_HM1 * B + bc] = hm1;
-    r[R_HLV0 * B + bc] = hv0; r[R_HLV1 * B + bc] = hv1;
-    r[R_LO * B + bc] = lo; r[R_S * B + bc] = s; r[R_TX * B + bc] = tx; r[R_TY * B + bc] = ty;
-    r[R_Y * B + bc] = y; r[R_Z * B + bc] = z;
-  }
+  const HeadOut h{__shfl(v, g0, LPI),     __shfl(v, g0 + 1, LPI), __shfl(v, g0 + 2, LPI),
+                  __shfl(v, g0 + 3, LPI), __shfl(v, g0 + 4, LPI), __shfl(v, g0 + 5, LPI),
+                  __shfl(v, g0 + 6, LPI)};
+  // the step's state-free values, in every lane (lane 0 of each group shuffles them below)
+  const StepVals sv = step_values(cfg, pbias, h, e_s, e_h0, e_h1, uu);
+  if (b < B && t < T && j == 0)
+    step_values_store(io, rb, io.rec + (size_t)tc * R_NREC * B, B, bc, h, sv);
   // the loop state, step by step (lane 0 of the image; every lane shuffles)
   float zs[MAX_STEPS_FWD], zk[MAX_STEPS_FWD], ke[MAX_STEPS_FWD];
 #pragma unroll
   for (int u = 0; u < MAX_STEPS_FWD; ++u) {
     if (8 * u < LPI) {
-      zs[u] = __shfl(z, 8 * u, LPI);
-      zk[u] = __shfl(zkl, 8 * u, LPI);
-      ke[u] = __shfl(kl_end, 8 * u, LPI);
+      zs[u] = __shfl(sv.z, 8 * u, LPI);
+      zk[u] = __shfl(sv.zkl, 8 * u, LPI);
+      ke[u] = __shfl(sv.kl_end, 8 * u, LPI);
     }
   }
   if (b >= B || li != 0) return;
@@ -901,18 +846,6 @@ __global__ __launch_bounds__(1024) void batch_mean_kernel(const float* a0, const
   }
 }
 
-// column sums of X [R, N] (row stride ld) -> atomically added into out[N]
-__global__ __launch_bounds__(256) void colsum_kernel(const float* X, int R, int N, int ld,
-                                                     int rows_per_block, float* out) {
-  const int col = blockIdx.x * 256 + threadIdx.x;
-  if (col >= N) return;
-  const int r0 = blockIdx.y * rows_per_block;
-  const int r1 = min(R, r0 + rows_per_block);
-  float s = 0.0f;
-  for (int r = r0; r < r1; ++r) s += X[(size_t)r * ld + col];
-  atomicAdd(out + col, s);
-}
-
 // Up to 8 buffers filled with a 32-bit pattern in one launch (the step's
 // loop-state resets: stopping sum, running loss, counts, live flags; the
 // gradient buffer): grid row j covers buffer j.
@@ -1314,15 +1247,6 @@ extern "C" int mog_heads_output_wgrad(int nheads, const float* const* hid,
   hipStream_t s = mog_stream(stream);
   heads_out_partial_kernel<<<dim3(a.S, nheads), 256, 0, s>>>(a);
   heads_out_reduce_kernel<<<nheads, 256, 0, s>>>(a);
-  MOG_LAUNCH_RET();
-}
-
-extern "C" int mog_colsum_add(const float* X, int R, int N, int ld, float* out, void* stream) {
-  MOG_CHECK_ARG(X && out && R >= 0 && N >= 0);
-  if (R == 0 || N == 0) return 0;
-  const int rpb = 256;
-  dim3 g(mog_cdiv(N, 256), mog_cdiv(R, rpb));
-  colsum_kernel<<<g, 256, 0, mog_stream(stream)>>>(X, R, N, ld, rpb, out);
   MOG_LAUNCH_RET();
 }
 

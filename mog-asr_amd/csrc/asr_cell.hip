@@ -7,6 +7,7 @@
 // the gradient at ties to the first operand, ReduceMin splits it evenly over
 // tied minima, Abs' = sign).
 #include "mog_common.h"
+#include "step_math.h"
 
 namespace {
 
@@ -59,43 +60,7 @@ struct AsrHid {
                  // 8/9 gen_scale m/v (raw -> finished; null with the fixed scale prior)
 };
 
-constexpr int HS = 64;
-
-// one k-ordered fma chain; the operands of 32 k-steps loaded before their
-// fmas (one memory round trip per 32 k, not per k; same bits)
-__device__ __forceinline__ float chain64(const float* a, const float* w, int ldw) {
-#pragma clang fp contract(off)
-  float acc = 0.0f;
-#pragma unroll
-  for (int k0 = 0; k0 < HS; k0 += 32) {
-    float av[32], wv[32];
-#pragma unroll
-    for (int i = 0; i < 32; ++i) {
-      av[i] = a[k0 + i];
-      wv[i] = w[(size_t)(k0 + i) * ldw];
-    }
-#pragma unroll
-    for (int i = 0; i < 32; ++i) acc = fmaf(av[i], wv[i], acc);
-  }
-  return acc;
-}
-
-__device__ __forceinline__ float lse0(float a) {
-#pragma clang fp contract(off)
-  float m = a > 0.0f ? a : 0.0f;
-  if (!(m - m == 0.0f)) m = 0.0f;
-  return mog_logf(mog_expf(0.0f - m) + mog_expf(a - m)) + m;
-}
-
-__device__ __forceinline__ float concrete_kl(float y, float plo, float pT, float qlo, float qT) {
-#pragma clang fp contract(off)
-  const float eps = 1e-9f;
-  const float lse_p = lse0(-y * pT + plo);
-  const float log_prior = ((mog_logf(pT + eps) - y * (pT + 1.0f)) + plo) - 2.0f * lse_p;
-  const float lse_q = lse0(-y * qT + qlo);
-  const float log_post = ((mog_logf(qT + eps) - y * (qT + 1.0f)) + qlo) - 2.0f * lse_q;
-  return log_post - log_prior;
-}
+constexpr int HS = 64;  // hidden units of every head (step_math.h chain64)
 
 // U rows [z_prev (Z) | ss_prev (3) | h_prev (H) | 0 pad] (the LSTMCell input
 // concat order, :403-412 / :457-463); null sources are zeros (step 0)
@@ -322,9 +287,7 @@ __global__ __launch_bounds__(256) void asr_step_fwd_kernel(AsrCfg cfg, AsrW W, A
   io.shift[2 * b] = tx;
   io.shift[2 * b + 1] = ty;
   // z_pres (:604-620)
-  const float eps = 1e-9f;
-  const float noise = mog_logf(uu + eps) - mog_logf((1.0f - uu) + eps);
-  const float y = (lo + noise) / cfg.temperature;
+  const float y = (lo + logistic_noise(uu)) / cfg.temperature;
   float z = mog_sigmoidf(y);
   if (!cfg.train) z = rintf(z);
   const float zprob = mog_sigmoidf(lo);
@@ -852,21 +815,25 @@ static int fill_gw(AsrGW& GW, const float* const* gw) {
   return 1;
 }
 
-// gw == null: the fixed scale prior (hid[8]); else the learned one (hid[10])
-static int asr_step_forward(int B, int step, int train, int fix_steps, float thr,
-                            float temperature, float scale_prior_mean, float scale_prior_var,
-                            float scale_prior_logvar, float gamma_num, const float* const* w,
-                            const float* const* gw, float* const* hid, const float* eps_shift,
-                            const float* eps_scale, const float* u, float* stop, int* digits,
-                            int* live, float* rec, float* theta_fwd, float* theta_back,
-                            float* ss, float* scale, float* shift, float* zprob, float* zmask,
-                            float* zval, float* zc, void* stream) {
+// gw == null: the fixed scale prior (hid[8]); else the learned one (hid[10]),
+// which reads no constant prior: the kernel config then holds N(0, 1)
+// whatever the caller passed
+extern "C" int mog_asr_step_forward(int B, int step, int train, int fix_steps, float thr,
+                                    float temperature, float scale_prior_mean,
+                                    float scale_prior_var, float scale_prior_logvar,
+                                    float gamma_num, const float* const* w,
+                                    const float* const* gw, float* const* hid,
+                                    const float* eps_shift, const float* eps_scale,
+                                    const float* u, float* stop, int* digits, int* live,
+                                    float* rec, float* theta_fwd, float* theta_back, float* ss,
+                                    float* scale, float* shift, float* zprob, float* zmask,
+                                    float* zval, float* zc, void* stream) {
   MOG_CHECK_ARG(B >= 0 && w && hid && eps_shift && eps_scale && u && stop && digits && live);
   MOG_CHECK_ARG(rec && theta_fwd && theta_back && ss && scale && shift && zprob && zmask && zval &&
                 zc);
   if (B == 0) return 0;
-  AsrCfg c{B, step, train, fix_steps, thr, temperature, scale_prior_mean, scale_prior_var,
-           scale_prior_logvar, gamma_num, 0.0f};
+  AsrCfg c{B, step, train, fix_steps, thr, temperature, gw ? 0.0f : scale_prior_mean,
+           gw ? 1.0f : scale_prior_var, gw ? 0.0f : scale_prior_logvar, gamma_num, 0.0f};
   AsrW W;
   MOG_CHECK_ARG(fill_w(W, w));
   AsrGW GW{};
@@ -883,36 +850,6 @@ static int asr_step_forward(int B, int step, int train, int fix_steps, float thr
   else
     asr_step_fwd_kernel<false><<<mog_cdiv(B, 4), 256, 0, mog_stream(stream)>>>(c, W, GW, hp, io);
   MOG_LAUNCH_RET();
-}
-
-extern "C" int mog_asr_step_forward(int B, int step, int train, int fix_steps, float thr,
-                                    float temperature, float scale_prior_mean,
-                                    float scale_prior_var, float scale_prior_logvar,
-                                    float gamma_num, const float* const* w, float* const* hid,
-                                    const float* eps_shift, const float* eps_scale,
-                                    const float* u, float* stop, int* digits, int* live,
-                                    float* rec, float* theta_fwd, float* theta_back, float* ss,
-                                    float* scale, float* shift, float* zprob, float* zmask,
-                                    float* zval, float* zc, void* stream) {
-  return asr_step_forward(B, step, train, fix_steps, thr, temperature, scale_prior_mean,
-                          scale_prior_var, scale_prior_logvar, gamma_num, w, nullptr, hid,
-                          eps_shift, eps_scale, u, stop, digits, live, rec, theta_fwd, theta_back,
-                          ss, scale, shift, zprob, zmask, zval, zc, stream);
-}
-
-extern "C" int mog_asr_step_forward_learned(int B, int step, int train, int fix_steps, float thr,
-                                            float temperature, float gamma_num,
-                                            const float* const* w, const float* const* gw,
-                                            float* const* hid, const float* eps_shift,
-                                            const float* eps_scale, const float* u, float* stop,
-                                            int* digits, int* live, float* rec, float* theta_fwd,
-                                            float* theta_back, float* ss, float* scale,
-                                            float* shift, float* zprob, float* zmask, float* zval,
-                                            float* zc, void* stream) {
-  MOG_CHECK_ARG(gw);
-  return asr_step_forward(B, step, train, fix_steps, thr, temperature, 0.0f, 1.0f, 0.0f, gamma_num,
-                          w, gw, hid, eps_shift, eps_scale, u, stop, digits, live, rec, theta_fwd,
-                          theta_back, ss, scale, shift, zprob, zmask, zval, zc, stream);
 }
 
 static int fill_loss_cfg(AsrLossCfg& c, int B, int T, int C, int nc, const int* cons,
@@ -966,18 +903,20 @@ extern "C" int mog_asr_terms_backward(int B, int T, int C, int nc, const int* co
   MOG_LAUNCH_RET();
 }
 
-static int asr_step_backward(int B, int train, int fix_steps, float temperature,
-                             float scale_prior_mean, float scale_prior_var, float grad_scale,
-                             const float* const* w, const float* const* gw, float* const* hid,
-                             const float* rec, const float* eps_shift, const float* eps_scale,
-                             const float* dtheta_fwd, const float* dtheta_back, const float* dot,
-                             const float* dreg, const float* dss, float* douts,
-                             float* const* dpre, void* stream) {
+// gw as in mog_asr_step_forward (hid / dpre [10] and douts [B][14] with it)
+extern "C" int mog_asr_step_backward(int B, int train, int fix_steps, float temperature,
+                                     float scale_prior_mean, float scale_prior_var,
+                                     float grad_scale, const float* const* w,
+                                     const float* const* gw, float* const* hid, const float* rec,
+                                     const float* eps_shift, const float* eps_scale,
+                                     const float* dtheta_fwd, const float* dtheta_back,
+                                     const float* dot, const float* dreg, const float* dss,
+                                     float* douts, float* const* dpre, void* stream) {
   MOG_CHECK_ARG(B >= 0 && w && hid && rec && eps_shift && eps_scale && dtheta_fwd && dtheta_back);
   MOG_CHECK_ARG(dot && dreg && douts && dpre);
   if (B == 0) return 0;
-  AsrCfg c{B, 0, train, fix_steps, 0.0f, temperature, scale_prior_mean, scale_prior_var, 0.0f,
-           0.0f, grad_scale};
+  AsrCfg c{B, 0, train, fix_steps, 0.0f, temperature, gw ? 0.0f : scale_prior_mean,
+           gw ? 1.0f : scale_prior_var, 0.0f, 0.0f, grad_scale};
   AsrW W;
   MOG_CHECK_ARG(fill_w(W, w));
   AsrGW GW{};
@@ -996,31 +935,4 @@ static int asr_step_backward(int B, int train, int fix_steps, float temperature,
   else
     asr_step_bwd_kernel<false><<<mog_cdiv(B, 4), 256, 0, mog_stream(stream)>>>(c, W, GW, hp, io);
   MOG_LAUNCH_RET();
-}
-
-extern "C" int mog_asr_step_backward(int B, int train, int fix_steps, float temperature,
-                                     float scale_prior_mean, float scale_prior_var,
-                                     float grad_scale, const float* const* w,
-                                     float* const* hid, const float* rec, const float* eps_shift,
-                                     const float* eps_scale, const float* dtheta_fwd,
-                                     const float* dtheta_back, const float* dot,
-                                     const float* dreg, const float* dss, float* douts,
-                                     float* const* dpre, void* stream) {
-  return asr_step_backward(B, train, fix_steps, temperature, scale_prior_mean, scale_prior_var,
-                           grad_scale, w, nullptr, hid, rec, eps_shift, eps_scale, dtheta_fwd,
-                           dtheta_back, dot, dreg, dss, douts, dpre, stream);
-}
-
-extern "C" int mog_asr_step_backward_learned(int B, int train, int fix_steps, float temperature,
-                                             float grad_scale, const float* const* w,
-                                             const float* const* gw, float* const* hid,
-                                             const float* rec, const float* eps_shift,
-                                             const float* eps_scale, const float* dtheta_fwd,
-                                             const float* dtheta_back, const float* dot,
-                                             const float* dreg, const float* dss, float* douts,
-                                             float* const* dpre, void* stream) {
-  MOG_CHECK_ARG(gw);
-  return asr_step_backward(B, train, fix_steps, temperature, 0.0f, 1.0f, grad_scale, w, gw, hid,
-                           rec, eps_shift, eps_scale, dtheta_fwd, dtheta_back, dot, dreg, dss,
-                           douts, dpre, stream);
 }

@@ -8,29 +8,11 @@
 // rounding per operation (contraction off), k-ordered fma chains, mog_math.h
 // transcendentals: the numerics of asr_cell.hip.
 #include "mog_common.h"
+#include "step_math.h"
 
 namespace {
 
-constexpr int HS = 64;
-
-// one k-ordered fma chain over the 64 hidden units (asr_cell.hip chain64: the
-// operands of 32 k-steps loaded before their fmas; same bits)
-__device__ __forceinline__ float chain64(const float* a, const float* w, int ldw) {
-#pragma clang fp contract(off)
-  float acc = 0.0f;
-#pragma unroll
-  for (int k0 = 0; k0 < HS; k0 += 32) {
-    float av[32], wv[32];
-#pragma unroll
-    for (int i = 0; i < 32; ++i) {
-      av[i] = a[k0 + i];
-      wv[i] = w[(size_t)(k0 + i) * ldw];
-    }
-#pragma unroll
-    for (int i = 0; i < 32; ++i) acc = fmaf(av[i], wv[i], acc);
-  }
-  return acc;
-}
+constexpr int HS = 64;  // hidden units of every head (step_math.h chain64)
 
 struct GenCfg {
   int G, Z, step, fix_steps;
@@ -152,8 +134,7 @@ __global__ __launch_bounds__(256) void asr_gen_step_kernel(GenCfg cfg, GenIO io)
   io.ss[(size_t)g * 3 + 1] = sl1;
   io.ss[(size_t)g * 3 + 2] = cl;
   // z_pres: concrete sample at the prior log-odds, always rounded (:1259-1285)
-  const float eps = 1e-9f;
-  const float noise = mog_logf(uu + eps) - mog_logf((1.0f - uu) + eps);
+  const float noise = logistic_noise(uu);
   const float y = (sv[m][4] + noise) / cfg.temperature;
   const float zp = rintf(mog_sigmoidf(y));
   // stopping sum, counts, canvas mask (:1287-1303)
@@ -191,21 +172,24 @@ __global__ __launch_bounds__(256) void bernoulli_threshold_kernel(const float* x
 
 }  // namespace
 
-// gw == null: the fixed scale prior; else gw[8] / ghid[2] of the learned one
-static int asr_gen_step(int G, int Z, int step, int fix_steps, float thr, float temperature,
-                        float scale_prior_mean, float scale_prior_var, float s,
-                        float vae_prior_mean, float vae_prior_logvar, const float* const* w,
-                        const float* const* hid, const float* const* gw,
-                        const float* const* ghid, const float* eps_shift, const float* eps_scale,
-                        const float* eps_z, const float* u, float* stop, int* digits, int* live,
-                        float* ss, float* z, float* theta_back, float* zval, float* zmask,
-                        void* stream) {
+// gw == null: the fixed scale prior; else gw[8] / ghid[2] of the learned one,
+// which reads no constant prior: the kernel config then holds N(0, 1)
+// whatever the caller passed
+extern "C" int mog_asr_gen_step(int G, int Z, int step, int fix_steps, float thr,
+                                float temperature, float scale_prior_mean, float scale_prior_var,
+                                float s, float vae_prior_mean, float vae_prior_logvar,
+                                const float* const* w, const float* const* hid,
+                                const float* const* gw, const float* const* ghid,
+                                const float* eps_shift, const float* eps_scale,
+                                const float* eps_z, const float* u, float* stop, int* digits,
+                                int* live, float* ss, float* z, float* theta_back, float* zval,
+                                float* zmask, void* stream) {
   MOG_CHECK_ARG(G >= 0 && Z > 0 && step >= 0 && s > 0.0f && w && hid && eps_shift && eps_scale && eps_z && u);
   MOG_CHECK_ARG(stop && digits && live && ss && z && theta_back && zval && zmask);
   MOG_CHECK_ARG(hid[0] && hid[1] && (hid[2] || fix_steps >= 0));
   if (G == 0) return 0;
-  GenCfg c{G, Z, step, fix_steps, thr, temperature, scale_prior_mean, scale_prior_var, s,
-           vae_prior_mean, vae_prior_logvar};
+  GenCfg c{G, Z, step, fix_steps, thr, temperature, gw ? 0.0f : scale_prior_mean,
+           gw ? 1.0f : scale_prior_var, s, vae_prior_mean, vae_prior_logvar};
   GenIO io{};
   io.hid_m = hid[0]; io.hid_v = hid[1]; io.hid_p = fix_steps >= 0 ? nullptr : hid[2];
   for (int i = 0; i < 6; ++i) {
@@ -227,35 +211,6 @@ static int asr_gen_step(int G, int Z, int step, int fix_steps, float thr, float 
     asr_gen_step_kernel<false><<<mog_cdiv(G, 4), 256, 0, mog_stream(stream)>>>(c, io);
   }
   MOG_LAUNCH_RET();
-}
-
-extern "C" int mog_asr_gen_step(int G, int Z, int step, int fix_steps, float thr,
-                                float temperature, float scale_prior_mean, float scale_prior_var,
-                                float s, float vae_prior_mean, float vae_prior_logvar,
-                                const float* const* w, const float* const* hid,
-                                const float* eps_shift, const float* eps_scale,
-                                const float* eps_z, const float* u, float* stop, int* digits,
-                                int* live, float* ss, float* z, float* theta_back, float* zval,
-                                float* zmask, void* stream) {
-  return asr_gen_step(G, Z, step, fix_steps, thr, temperature, scale_prior_mean, scale_prior_var,
-                      s, vae_prior_mean, vae_prior_logvar, w, hid, nullptr, nullptr, eps_shift,
-                      eps_scale, eps_z, u, stop, digits, live, ss, z, theta_back, zval, zmask,
-                      stream);
-}
-
-extern "C" int mog_asr_gen_step_learned(int G, int Z, int step, int fix_steps, float thr,
-                                        float temperature, float s, float vae_prior_mean,
-                                        float vae_prior_logvar, const float* const* w,
-                                        const float* const* hid, const float* const* gw,
-                                        const float* const* ghid, const float* eps_shift,
-                                        const float* eps_scale, const float* eps_z,
-                                        const float* u, float* stop, int* digits, int* live,
-                                        float* ss, float* z, float* theta_back, float* zval,
-                                        float* zmask, void* stream) {
-  MOG_CHECK_ARG(gw && ghid);
-  return asr_gen_step(G, Z, step, fix_steps, thr, temperature, 0.0f, 1.0f, s, vae_prior_mean,
-                      vae_prior_logvar, w, hid, gw, ghid, eps_shift, eps_scale, eps_z, u, stop,
-                      digits, live, ss, z, theta_back, zval, zmask, stream);
 }
 
 extern "C" int mog_bernoulli_threshold(const float* x, const float* u, float* out, long n,

@@ -388,18 +388,6 @@ extern "C" int mog_gemm_bf16(int batch, const void* const* A, const void* const*
 // dst[r][c] (ld_dst) = src[c][r] (transpose) or src[r][c]; rows x cols is the
 // destination extent, (src_rows, src_cols) the valid source extent.
 namespace {
-__global__ __launch_bounds__(256) void cvt_bf16_kernel(const float* src, int src_rows,
-                                                       int src_cols, int ld_src, __bf16* dst,
-                                                       int rows, int cols, int ld_dst,
-                                                       int transpose) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long)rows * cols) return;
-  const int r = i / cols, c = i - (long)r * cols;
-  const int sr = transpose ? c : r, sc = transpose ? r : c;
-  const float v = (sr < src_rows && sc < src_cols) ? src[(size_t)sr * ld_src + sc] : 0.0f;
-  dst[(size_t)r * ld_dst + c] = (__bf16)v;
-}
-
 // Up to 16 conversions in one launch (the bf16 weight packs of all VAE
 // layers after an optimizer step): job j covers elements [start[j], start[j+1]).
 constexpr int CVT_MAX = 16;
@@ -485,15 +473,5 @@ extern "C" int mog_cvt_bf16_batch(int njobs, const float* const* src, void* cons
   }
   if (njobs == 0 || mx == 0) return 0;
   cvt_bf16_batch_kernel<<<dim3(mog_cdiv(mx, 256), njobs), 256, 0, mog_stream(stream)>>>(b);
-  MOG_LAUNCH_RET();
-}
-
-extern "C" int mog_cvt_bf16(const float* src, int src_rows, int src_cols, int ld_src, void* dst,
-                            int rows, int cols, int ld_dst, int transpose, void* stream) {
-  MOG_CHECK_ARG(src && dst && rows >= 0 && cols >= 0);
-  if (rows == 0 || cols == 0) return 0;
-  cvt_bf16_kernel<<<mog_cdiv((long)rows * cols, 256), 256, 0, mog_stream(stream)>>>(
-      src, src_rows, src_cols, ld_src, reinterpret_cast<__bf16*>(dst), rows, cols, ld_dst,
-      transpose);
   MOG_LAUNCH_RET();
 }

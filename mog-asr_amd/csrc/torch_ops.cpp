@@ -1016,16 +1016,20 @@ void copy_f4_(const Tensor& src, Tensor dst) {
 }
 
 // ---------------------------------------------- AIR-ASR cells and losses ----
-// (air/air_number_bbox_location.py; records [T][30][B], asr_cell.hip)
-// douts: 12 columns, 14 with the learned scale prior (the *_learned_ ops)
+// (air/air_number_bbox_location.py; records [T][30][B], asr_cell.hip with the
+// loop-step numerics of step_math.h)
+// gw: the learned scale prior's gen_scale weights, [] with the fixed prior
+// (s_pm / s_pv / s_plv, which the learned prior does not read); with gw, hid
+// and dpre have 10 entries instead of 8 and douts 14 columns instead of 12
 constexpr int64_t ASR_NQ = 30, ASR_DN = 12, ASR_DNL = 14;
 
 // gen_scale dense W,b [258,64], dense_1 W,b [66,1], dense_2 W,b, dense_3 W,b
+// (none: the fixed scale prior)
 vector<void*> asr_gen_scale_weights(Op& o, at::TensorList gw) {
-  TORCH_CHECK(gw.size() == 8, o.name, ": 8 gen_scale tensors");
+  TORCH_CHECK(gw.empty() || gw.size() == 8, o.name, ": 0 or 8 gen_scale tensors");
   const int64_t ext[8] = {258 * 64, 64, 66, 1, 258 * 64, 64, 66, 1};
   vector<void*> p;
-  for (size_t k = 0; k < 8; ++k) p.push_back(o.f(gw[k], ext[k], "gw"));
+  for (size_t k = 0; k < gw.size(); ++k) p.push_back(o.f(gw[k], ext[k], "gw"));
   return p;
 }
 
@@ -1073,25 +1077,23 @@ void asr_unpack_parts_(int64_t B, int64_t Z, int64_t H, int64_t ld, const Tensor
         o.name);
 }
 
-// learned: the gen_scale heads' scale prior (gw[8], hid[10]) instead of the
-// constant one (s_pm / s_pv / s_plv)
-void asr_step_forward_impl(const char* name, bool learned, int64_t B, int64_t step, bool train,
-                           int64_t fix_steps, double thr, double temperature, double s_pm,
-                           double s_pv, double s_plv, double gamma_num, at::TensorList w,
-                           at::TensorList gw, const c10::List<optional<Tensor>>& hid,
-                           const Tensor& eps_shift, const Tensor& eps_scale, const Tensor& u,
-                           Tensor stop, Tensor digits, Tensor live, Tensor rec, Tensor theta_fwd,
-                           Tensor theta_back, Tensor ss, Tensor scale, Tensor shift, Tensor zprob,
-                           Tensor zmask, Tensor zval, Tensor zc) {
-  Op o(name);
+void asr_step_forward_(int64_t B, int64_t step, bool train, int64_t fix_steps, double thr,
+                       double temperature, double s_pm, double s_pv, double s_plv,
+                       double gamma_num, at::TensorList w, at::TensorList gw,
+                       const c10::List<optional<Tensor>>& hid, const Tensor& eps_shift,
+                       const Tensor& eps_scale, const Tensor& u, Tensor stop, Tensor digits,
+                       Tensor live, Tensor rec, Tensor theta_fwd, Tensor theta_back, Tensor ss,
+                       Tensor scale, Tensor shift, Tensor zprob, Tensor zmask, Tensor zval,
+                       Tensor zc) {
+  Op o("asr_step_forward_");
+  auto pg = asr_gen_scale_weights(o, gw);
+  const bool learned = !pg.empty();
   const size_t nh = learned ? 10 : 8;
   TORCH_CHECK(w.size() == 20 && hid.size() == nh, o.name, ": 10 output layers, ", nh,
               " hidden layers");
   TORCH_CHECK(step >= 0, o.name, ": step");
   float* pst = o.f(stop, B, "stop");
   auto pw = o.list(w, F32, 1, "w");
-  vector<void*> pg;
-  if (learned) pg = asr_gen_scale_weights(o, gw);
   auto ph = o.list(hid, F32, B * 64, "hid");
   float* peh = o.f(eps_shift, 2 * B, "eps_shift");
   float* pes = o.f(eps_scale, B, "eps_scale");
@@ -1109,66 +1111,32 @@ void asr_step_forward_impl(const char* name, bool learned, int64_t B, int64_t st
   float* pzv = o.f(zval, B, "zval");
   float* pzc = o.f(zc, B, "zc");
   GUARD(o);
-  if (learned) {
+  if (learned)
     for (size_t k = 0; k < nh; ++k)
       TORCH_CHECK(ph[k] || (k == 5 && fix_steps >= 0), o.name, ": hid[", k, "] is None");
-    check(mog_asr_step_forward_learned(B, step, train, fix_steps, thr, temperature, gamma_num,
-                                       arr<float>(pw), arr<float>(pg), marr<float>(ph), peh, pes,
-                                       pu, pst, pd, pl, pr, ptf, ptb, pss, psc, psh, pzp, pzm,
-                                       pzv, pzc, o.stream()),
-          o.name);
-    return;
-  }
   check(mog_asr_step_forward(B, step, train, fix_steps, thr, temperature, s_pm, s_pv, s_plv,
-                             gamma_num, arr<float>(pw), marr<float>(ph), peh, pes, pu, pst, pd, pl,
-                             pr, ptf, ptb, pss, psc, psh, pzp, pzm, pzv, pzc, o.stream()),
+                             gamma_num, arr<float>(pw), arr<float>(pg), marr<float>(ph), peh, pes,
+                             pu, pst, pd, pl, pr, ptf, ptb, pss, psc, psh, pzp, pzm, pzv, pzc,
+                             o.stream()),
         o.name);
 }
 
-void asr_step_forward_(int64_t B, int64_t step, bool train, int64_t fix_steps, double thr,
-                       double temperature, double s_pm, double s_pv, double s_plv,
-                       double gamma_num, at::TensorList w, const c10::List<optional<Tensor>>& hid,
-                       const Tensor& eps_shift, const Tensor& eps_scale, const Tensor& u,
-                       Tensor stop, Tensor digits, Tensor live, Tensor rec, Tensor theta_fwd,
-                       Tensor theta_back, Tensor ss, Tensor scale, Tensor shift, Tensor zprob,
-                       Tensor zmask, Tensor zval, Tensor zc) {
-  asr_step_forward_impl("asr_step_forward_", false, B, step, train, fix_steps, thr, temperature,
-                        s_pm, s_pv, s_plv, gamma_num, w, {}, hid, eps_shift, eps_scale, u, stop,
-                        digits, live, rec, theta_fwd, theta_back, ss, scale, shift, zprob, zmask,
-                        zval, zc);
-}
-
-void asr_step_forward_learned_(int64_t B, int64_t step, bool train, int64_t fix_steps, double thr,
-                               double temperature, double gamma_num, at::TensorList w,
-                               at::TensorList gw, const c10::List<optional<Tensor>>& hid,
-                               const Tensor& eps_shift, const Tensor& eps_scale, const Tensor& u,
-                               Tensor stop, Tensor digits, Tensor live, Tensor rec,
-                               Tensor theta_fwd, Tensor theta_back, Tensor ss, Tensor scale,
-                               Tensor shift, Tensor zprob, Tensor zmask, Tensor zval, Tensor zc) {
-  asr_step_forward_impl("asr_step_forward_learned_", true, B, step, train, fix_steps, thr,
-                        temperature, 0.0, 1.0, 0.0, gamma_num, w, gw, hid, eps_shift, eps_scale, u,
-                        stop, digits, live, rec, theta_fwd, theta_back, ss, scale, shift, zprob,
-                        zmask, zval, zc);
-}
-
 // one step of the generation loop (asr_gen.hip; :1124-1361)
-void asr_gen_step_impl(const char* name, bool learned, int64_t G, int64_t Z, int64_t step,
-                       int64_t fix_steps, double thr, double temperature, double s_pm,
-                       double s_pv, double s, double v_pm, double v_plv,
-                       const c10::List<optional<Tensor>>& w,
-                       const c10::List<optional<Tensor>>& hid, at::TensorList gw,
-                       at::TensorList ghid, const Tensor& eps_shift, const Tensor& eps_scale,
-                       const Tensor& eps_z, const Tensor& u, Tensor stop, Tensor digits,
-                       Tensor live, Tensor ss, Tensor z, Tensor theta_back, Tensor zval,
-                       Tensor zmask) {
-  Op o(name);
+// (ghid: the two gen_scale chains over hg, [] with gw == [])
+void asr_gen_step_(int64_t G, int64_t Z, int64_t step, int64_t fix_steps, double thr,
+                   double temperature, double s_pm, double s_pv, double s, double v_pm,
+                   double v_plv, const c10::List<optional<Tensor>>& w,
+                   const c10::List<optional<Tensor>>& hid, at::TensorList gw,
+                   at::TensorList ghid, const Tensor& eps_shift, const Tensor& eps_scale,
+                   const Tensor& eps_z, const Tensor& u, Tensor stop, Tensor digits, Tensor live,
+                   Tensor ss, Tensor z, Tensor theta_back, Tensor zval, Tensor zmask) {
+  Op o("asr_gen_step_");
   TORCH_CHECK(w.size() == 6 && hid.size() == 3, o.name, ": 3 output layers, 3 hidden layers");
-  vector<void*> pg, pgh;
-  if (learned) {
-    TORCH_CHECK(ghid.size() == 2, o.name, ": 2 gen_scale hidden layers");
-    pg = asr_gen_scale_weights(o, gw);
-    pgh = o.list(ghid, F32, G * 64, "ghid");
-  }
+  auto pg = asr_gen_scale_weights(o, gw);
+  const bool learned = !pg.empty();
+  TORCH_CHECK(ghid.size() == (learned ? 2u : 0u), o.name, ": ", learned ? 2 : 0,
+              " gen_scale hidden layers");
+  auto pgh = o.list(ghid, F32, G * 64, "ghid");
   TORCH_CHECK(step >= 0, o.name, ": step");
   float* pst = o.f(stop, G, "stop");
   // gen_shift dense_1 / dense_3 [64,2] + [2], z_pres/prior dense_1 [64,1] + [1]
@@ -1189,44 +1157,10 @@ void asr_gen_step_impl(const char* name, bool learned, int64_t G, int64_t Z, int
   float* pzv = o.f(zval, G, "zval");
   float* pzm = o.f(zmask, G, "zmask");
   GUARD(o);
-  if (learned) {
-    check(mog_asr_gen_step_learned(G, Z, step, fix_steps, thr, temperature, s, v_pm, v_plv,
-                                   arr<float>(pw), arr<float>(ph), arr<float>(pg),
-                                   arr<float>(pgh), peh, pes, pez, pu, pst, pd, pl, pss, pz, ptb,
-                                   pzv, pzm, o.stream()),
-          o.name);
-    return;
-  }
   check(mog_asr_gen_step(G, Z, step, fix_steps, thr, temperature, s_pm, s_pv, s, v_pm, v_plv,
-                         arr<float>(pw), arr<float>(ph), peh, pes, pez, pu, pst, pd, pl, pss, pz,
-                         ptb, pzv, pzm, o.stream()),
+                         arr<float>(pw), arr<float>(ph), arr<float>(pg), arr<float>(pgh), peh, pes,
+                         pez, pu, pst, pd, pl, pss, pz, ptb, pzv, pzm, o.stream()),
         o.name);
-}
-
-void asr_gen_step_(int64_t G, int64_t Z, int64_t step, int64_t fix_steps, double thr,
-                   double temperature, double s_pm, double s_pv, double s, double v_pm,
-                   double v_plv, const c10::List<optional<Tensor>>& w,
-                   const c10::List<optional<Tensor>>& hid, const Tensor& eps_shift,
-                   const Tensor& eps_scale, const Tensor& eps_z, const Tensor& u, Tensor stop,
-                   Tensor digits, Tensor live, Tensor ss, Tensor z, Tensor theta_back, Tensor zval,
-                   Tensor zmask) {
-  asr_gen_step_impl("asr_gen_step_", false, G, Z, step, fix_steps, thr, temperature, s_pm, s_pv, s,
-                    v_pm, v_plv, w, hid, {}, {}, eps_shift, eps_scale, eps_z, u, stop, digits,
-                    live, ss, z, theta_back, zval, zmask);
-}
-
-// the learned scale prior: the gen_scale chains over hg (ghid) and weights (gw)
-void asr_gen_step_learned_(int64_t G, int64_t Z, int64_t step, int64_t fix_steps, double thr,
-                           double temperature, double s, double v_pm, double v_plv,
-                           const c10::List<optional<Tensor>>& w,
-                           const c10::List<optional<Tensor>>& hid, at::TensorList gw,
-                           at::TensorList ghid, const Tensor& eps_shift, const Tensor& eps_scale,
-                           const Tensor& eps_z, const Tensor& u, Tensor stop, Tensor digits,
-                           Tensor live, Tensor ss, Tensor z, Tensor theta_back, Tensor zval,
-                           Tensor zmask) {
-  asr_gen_step_impl("asr_gen_step_learned_", true, G, Z, step, fix_steps, thr, temperature, 0.0,
-                    1.0, s, v_pm, v_plv, w, hid, gw, ghid, eps_shift, eps_scale, eps_z, u, stop,
-                    digits, live, ss, z, theta_back, zval, zmask);
 }
 
 void bernoulli_threshold_(const Tensor& x, const Tensor& u, Tensor out, int64_t n) {
@@ -1305,22 +1239,21 @@ void asr_terms_backward_(int64_t B, int64_t T, int64_t C, at::IntArrayRef cons,
         o.name);
 }
 
-void asr_step_backward_impl(const char* name, bool learned, int64_t B, bool train,
-                            int64_t fix_steps, double temperature, double s_pm, double s_pv,
-                            double grad_scale, at::TensorList w, at::TensorList gw,
-                            const c10::List<optional<Tensor>>& hid, const Tensor& rec,
-                            const Tensor& eps_shift, const Tensor& eps_scale,
-                            const Tensor& dtheta_fwd, const Tensor& dtheta_back,
-                            const Tensor& dot, const Tensor& dreg, const optional<Tensor>& dss,
-                            Tensor douts, const c10::List<optional<Tensor>>& dpre) {
-  Op o(name);
+void asr_step_backward_(int64_t B, bool train, int64_t fix_steps, double temperature,
+                        double s_pm, double s_pv, double grad_scale, at::TensorList w,
+                        at::TensorList gw, const c10::List<optional<Tensor>>& hid,
+                        const Tensor& rec, const Tensor& eps_shift, const Tensor& eps_scale,
+                        const Tensor& dtheta_fwd, const Tensor& dtheta_back, const Tensor& dot,
+                        const Tensor& dreg, const optional<Tensor>& dss, Tensor douts,
+                        const c10::List<optional<Tensor>>& dpre) {
+  Op o("asr_step_backward_");
+  auto pg = asr_gen_scale_weights(o, gw);
+  const bool learned = !pg.empty();
   const size_t nh = learned ? 10 : 8;
   TORCH_CHECK(w.size() == 20 && hid.size() == nh && dpre.size() == nh, o.name,
               ": 10 output layers, ", nh, " hidden layers");
   float* pdo = o.f(douts, B * (learned ? ASR_DNL : ASR_DN), "douts");
   auto pw = o.list(w, F32, 1, "w");
-  vector<void*> pg;
-  if (learned) pg = asr_gen_scale_weights(o, gw);
   auto ph = o.list(hid, F32, B * 64, "hid");
   auto pdp = o.list(dpre, F32, B * 64, "dpre");
   float* prec = o.f(rec, ASR_NQ * B, "rec");
@@ -1332,43 +1265,10 @@ void asr_step_backward_impl(const char* name, bool learned, int64_t B, bool trai
   float* pdr = o.f(dreg, 4 * B, "dreg");
   float* pds = o.f(dss, 3 * B, "dss");
   GUARD(o);
-  if (learned) {
-    check(mog_asr_step_backward_learned(B, train, fix_steps, temperature, grad_scale,
-                                        arr<float>(pw), arr<float>(pg), marr<float>(ph), prec, peh,
-                                        pes, ptf, ptb, pd, pdr, pds, pdo, marr<float>(pdp),
-                                        o.stream()),
-          o.name);
-    return;
-  }
   check(mog_asr_step_backward(B, train, fix_steps, temperature, s_pm, s_pv, grad_scale,
-                              arr<float>(pw), marr<float>(ph), prec, peh, pes, ptf, ptb, pd, pdr,
-                              pds, pdo, marr<float>(pdp), o.stream()),
+                              arr<float>(pw), arr<float>(pg), marr<float>(ph), prec, peh, pes, ptf,
+                              ptb, pd, pdr, pds, pdo, marr<float>(pdp), o.stream()),
         o.name);
-}
-
-void asr_step_backward_(int64_t B, bool train, int64_t fix_steps, double temperature,
-                        double s_pm, double s_pv, double grad_scale, at::TensorList w,
-                        const c10::List<optional<Tensor>>& hid, const Tensor& rec,
-                        const Tensor& eps_shift, const Tensor& eps_scale,
-                        const Tensor& dtheta_fwd, const Tensor& dtheta_back, const Tensor& dot,
-                        const Tensor& dreg, const optional<Tensor>& dss, Tensor douts,
-                        const c10::List<optional<Tensor>>& dpre) {
-  asr_step_backward_impl("asr_step_backward_", false, B, train, fix_steps, temperature, s_pm, s_pv,
-                         grad_scale, w, {}, hid, rec, eps_shift, eps_scale, dtheta_fwd,
-                         dtheta_back, dot, dreg, dss, douts, dpre);
-}
-
-void asr_step_backward_learned_(int64_t B, bool train, int64_t fix_steps, double temperature,
-                                double grad_scale, at::TensorList w, at::TensorList gw,
-                                const c10::List<optional<Tensor>>& hid, const Tensor& rec,
-                                const Tensor& eps_shift, const Tensor& eps_scale,
-                                const Tensor& dtheta_fwd, const Tensor& dtheta_back,
-                                const Tensor& dot, const Tensor& dreg,
-                                const optional<Tensor>& dss, Tensor douts,
-                                const c10::List<optional<Tensor>>& dpre) {
-  asr_step_backward_impl("asr_step_backward_learned_", true, B, train, fix_steps, temperature, 0.0,
-                         1.0, grad_scale, w, gw, hid, rec, eps_shift, eps_scale, dtheta_fwd,
-                         dtheta_back, dot, dreg, dss, douts, dpre);
 }
 
 }  // namespace
@@ -1741,29 +1641,17 @@ TORCH_LIBRARY_FRAGMENT(mog_air, m) {
   m.def(
       "asr_step_forward_(int B, int step, bool train, int fix_steps, float thr, "
       "float temperature, float s_pm, float s_pv, float s_plv, float gamma_num, Tensor[] w, "
-      "Tensor(a!)?[] hid, Tensor eps_shift, Tensor eps_scale, Tensor u, Tensor(b!) stop, "
-      "Tensor(c!) digits, Tensor(d!) live, Tensor(e!) rec, Tensor(f!) theta_fwd, "
-      "Tensor(g!) theta_back, Tensor(h!) ss, Tensor(i!) scale, Tensor(j!) shift, "
-      "Tensor(k!) zprob, Tensor(l!) zmask, Tensor(m!) zval, Tensor(n!) zc) -> ()");
-  m.def(
-      "asr_step_forward_learned_(int B, int step, bool train, int fix_steps, float thr, "
-      "float temperature, float gamma_num, Tensor[] w, Tensor[] gw, "
-      "Tensor(a!)?[] hid, Tensor eps_shift, Tensor eps_scale, Tensor u, Tensor(b!) stop, "
-      "Tensor(c!) digits, Tensor(d!) live, Tensor(e!) rec, Tensor(f!) theta_fwd, "
-      "Tensor(g!) theta_back, Tensor(h!) ss, Tensor(i!) scale, Tensor(j!) shift, "
-      "Tensor(k!) zprob, Tensor(l!) zmask, Tensor(m!) zval, Tensor(n!) zc) -> ()");
-  m.def(
-      "asr_gen_step_learned_(int G, int Z, int step, int fix_steps, float thr, "
-      "float temperature, float s, float v_pm, float v_plv, Tensor?[] w, Tensor?[] hid, "
-      "Tensor[] gw, Tensor[] ghid, Tensor eps_shift, Tensor eps_scale, Tensor eps_z, Tensor u, "
-      "Tensor(a!) stop, Tensor(b!) digits, Tensor(c!) live, Tensor(d!) ss, Tensor(e!) z, "
-      "Tensor(f!) theta_back, Tensor(g!) zval, Tensor(h!) zmask) -> ()");
+      "Tensor[] gw, Tensor(a!)?[] hid, Tensor eps_shift, Tensor eps_scale, Tensor u, "
+      "Tensor(b!) stop, Tensor(c!) digits, Tensor(d!) live, Tensor(e!) rec, "
+      "Tensor(f!) theta_fwd, Tensor(g!) theta_back, Tensor(h!) ss, Tensor(i!) scale, "
+      "Tensor(j!) shift, Tensor(k!) zprob, Tensor(l!) zmask, Tensor(m!) zval, "
+      "Tensor(n!) zc) -> ()");
   m.def(
       "asr_gen_step_(int G, int Z, int step, int fix_steps, float thr, float temperature, "
       "float s_pm, float s_pv, float s, float v_pm, float v_plv, Tensor?[] w, Tensor?[] hid, "
-      "Tensor eps_shift, Tensor eps_scale, Tensor eps_z, Tensor u, Tensor(a!) stop, "
-      "Tensor(b!) digits, Tensor(c!) live, Tensor(d!) ss, Tensor(e!) z, Tensor(f!) theta_back, "
-      "Tensor(g!) zval, Tensor(h!) zmask) -> ()");
+      "Tensor[] gw, Tensor[] ghid, Tensor eps_shift, Tensor eps_scale, Tensor eps_z, Tensor u, "
+      "Tensor(a!) stop, Tensor(b!) digits, Tensor(c!) live, Tensor(d!) ss, Tensor(e!) z, "
+      "Tensor(f!) theta_back, Tensor(g!) zval, Tensor(h!) zmask) -> ()");
   m.def("bernoulli_threshold_(Tensor x, Tensor u, Tensor(a!) out, int n) -> ()");
   m.def(
       "eval_detection_(Tensor gt_boxes, Tensor gt_num, int N, int G, Tensor shifts, "
@@ -1787,14 +1675,9 @@ TORCH_LIBRARY_FRAGMENT(mog_air, m) {
       "float inv_batch_global, Tensor rec, Tensor live, Tensor zsum, Tensor(a!) dreg) -> ()");
   m.def(
       "asr_step_backward_(int B, bool train, int fix_steps, float temperature, float s_pm, "
-      "float s_pv, float grad_scale, Tensor[] w, Tensor?[] hid, Tensor rec, Tensor eps_shift, "
-      "Tensor eps_scale, Tensor dtheta_fwd, Tensor dtheta_back, Tensor dot, Tensor dreg, "
-      "Tensor? dss, Tensor(a!) douts, Tensor(b!)?[] dpre) -> ()");
-  m.def(
-      "asr_step_backward_learned_(int B, bool train, int fix_steps, float temperature, "
-      "float grad_scale, Tensor[] w, Tensor[] gw, Tensor?[] hid, Tensor rec, Tensor eps_shift, "
-      "Tensor eps_scale, Tensor dtheta_fwd, Tensor dtheta_back, Tensor dot, Tensor dreg, "
-      "Tensor? dss, Tensor(a!) douts, Tensor(b!)?[] dpre) -> ()");
+      "float s_pv, float grad_scale, Tensor[] w, Tensor[] gw, Tensor?[] hid, Tensor rec, "
+      "Tensor eps_shift, Tensor eps_scale, Tensor dtheta_fwd, Tensor dtheta_back, Tensor dot, "
+      "Tensor dreg, Tensor? dss, Tensor(a!) douts, Tensor(b!)?[] dpre) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(mog_air, CUDA, m) {
@@ -1850,9 +1733,6 @@ TORCH_LIBRARY_IMPL(mog_air, CUDA, m) {
   m.impl("asr_unpack_", &asr_unpack_);
   m.impl("asr_step_forward_", &asr_step_forward_);
   m.impl("asr_gen_step_", &asr_gen_step_);
-  m.impl("asr_step_forward_learned_", &asr_step_forward_learned_);
-  m.impl("asr_step_backward_learned_", &asr_step_backward_learned_);
-  m.impl("asr_gen_step_learned_", &asr_gen_step_learned_);
   m.impl("bernoulli_threshold_", &bernoulli_threshold_);
   m.impl("eval_detection_", &eval_detection_);
   m.impl("eval_detection_means_", &eval_detection_means_);

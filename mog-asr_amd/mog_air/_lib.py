@@ -67,11 +67,9 @@ _SIGS = {
     "mog_vae_sample_backward": [I, I, F, F, F, P, P, P, P, P, P, P, P, P, I, P],
     "mog_sigmoid_backward": [P, P, P, L, I, P],
     "mog_gemm_bf16": [I, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, F, I, P],
-    "mog_cvt_bf16": [P, I, I, I, P, I, I, I, I, P],
     "mog_cvt_bf16_batch": [I, P, P, P, P],
     "mog_recon_loss": [P, P, P, I, L, P, I, P, P, P, I, I, F, P, P, P, P, P, P, P],
     "mog_batch_mean": [P, P, P, P, I, P, P],
-    "mog_colsum_add": [P, I, I, I, P, P],
     "mog_heads_output_wgrad_work_elems": [I, I, I],
     "mog_heads_output_wgrad": [I, P, P, P, P, P, I, I, P, L, P],
     "mog_add": [P, P, P, L, P],
@@ -87,19 +85,12 @@ _SIGS = {
     "mog_asr_pack": [I, I, I, I, P, P, P, P, P, P, P],
     "mog_asr_unpack": [I, I, I, I, P, P, P, P, P, P, I, P],
     "mog_asr_unpack_parts": [I, I, I, I, P, P, I, L, P, P, P, P, I, P],
-    "mog_asr_step_forward": [I, I, I, I, F, F, F, F, F, F, P, P, P, P, P, P, P, P, P, P, P, P,
-                             P, P, P, P, P, P, P],
-    "mog_asr_step_forward_learned": [I, I, I, I, F, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P,
-                                     P, P, P, P, P, P, P],
+    "mog_asr_step_forward": [I, I, I, I] + [F] * 6 + [P] * 20,
     "mog_asr_terms": [I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
     "mog_asr_finalize": [I, I, I, I, P, P, F, P, P, P, P, P, P, P, P],
     "mog_asr_terms_backward": [I, I, I, I, P, P, F, F, P, P, P, P, P],
-    "mog_asr_step_backward": [I, I, I, F, F, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P],
-    "mog_asr_step_backward_learned": [I, I, I, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
-    "mog_asr_gen_step_learned": [I, I, I, I, F, F, F, F, F, P, P, P, P, P, P, P, P, P, P, P, P,
-                                 P, P, P, P, P],
-    "mog_asr_gen_step": [I, I, I, I, F, F, F, F, F, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P,
-                         P, P],
+    "mog_asr_step_backward": [I, I, I, F, F, F, F] + [P] * 14,
+    "mog_asr_gen_step": [I, I, I, I] + [F] * 7 + [P] * 17,
     "mog_bernoulli_threshold": [P, P, P, L, P],
     "mog_cnn_enc_images_per_wg": [I],
     "mog_cnn_enc_partial_elems": [I, I],

@@ -364,17 +364,10 @@ class AIRModel(ModelBase):
             outs = (ws.eps_shift[t], ws.eps_scale[t], ws.u[t], ws.stop, ws.digits, ws.live,
                     ws.arec[t], ws.th_f[t], ws.th_b[t], ws.ss[t], ws.scale[t], ws.shift[t],
                     ws.zprob[t], ws.zmask[t], ws.zval[t], ws.zc[t])
-            if learned:
-                _ops.asr_step_forward_learned_(B, t, self.train, fix, thr, temp,
-                                               float(self.hyper("constrains_num_gamma")), w20,
-                                               gw8, hid_l, *outs)
-            else:
-                _ops.asr_step_forward_(B, t, self.train, fix, thr, temp,
-                                       float(self.scale_prior_mean),
-                                       float(self.scale_prior_variance),
-                                       self.scale_prior_log_variance,
-                                       float(self.hyper("constrains_num_gamma")), w20, hid_l,
-                                       *outs)
+            _ops.asr_step_forward_(B, t, self.train, fix, thr, temp, float(self.scale_prior_mean),
+                                   float(self.scale_prior_variance), self.scale_prior_log_variance,
+                                   float(self.hyper("constrains_num_gamma")), w20,
+                                   gw8 if learned else [], hid_l, *outs)
             if self.live_hook is not None:
                 self.live_hook(ws.live, t)
             if self.fused_step:
@@ -489,16 +482,10 @@ class AIRModel(ModelBase):
                     ws.arec[t], ws.eps_shift[t], ws.eps_scale[t], ws.dth_f, ws.dth_b_all[t],
                     ws.dot_all[t], ws.dreg[t], ws.dss_carry if t < T - 1 else None, ws.douts[t],
                     [x if (k != 5 or fix < 0) else None for k, x in enumerate(dpre)])
-            if learned:
-                _ops.asr_step_backward_learned_(B, self.train, fix,
-                                                float(self.hyper("z_pres_temperature")),
-                                                float(gscale), w20, gw8, *tail)
-            else:
-                _ops.asr_step_backward_(B, self.train, fix,
-                                        float(self.hyper("z_pres_temperature")),
-                                        float(self.scale_prior_mean),
-                                        float(self.scale_prior_variance), float(gscale), w20,
-                                        *tail)
+            _ops.asr_step_backward_(B, self.train, fix, float(self.hyper("z_pres_temperature")),
+                                    float(self.scale_prior_mean),
+                                    float(self.scale_prior_variance), float(gscale), w20,
+                                    gw8 if learned else [], *tail)
             # dh[t] += the five heads reading h_t; dhg[t] += the generative shift
             # heads; dhg[t-1] += the prior at step t (it reads hg_{t-1}): three
             # chains of one shape in one launch
@@ -791,14 +778,10 @@ class AIRModel(ModelBase):
                 # the gen_scale hidden layers' chains over the new output (the
                 # kernel adds the shift latent's terms, bias and relu)
                 gemm([hg[cur]] * 2, gsc_w, [ghid[0], ghid[1]], G, 64, H, H, 64, 64, epi=EPI_STORE)
-                _ops.asr_gen_step_learned_(G, Z, t, fix, thr, temp, s, float(self.vae_prior_mean),
-                                           self.vae_prior_log_variance, w6, hid3, gw8,
-                                           [ghid[0], ghid[1]], *tail)
-            else:
-                _ops.asr_gen_step_(G, Z, t, fix, thr, temp, float(self.scale_prior_mean),
-                                   float(self.scale_prior_variance), s,
-                                   float(self.vae_prior_mean), self.vae_prior_log_variance, w6,
-                                   hid3, *tail)
+            _ops.asr_gen_step_(G, Z, t, fix, thr, temp, float(self.scale_prior_mean),
+                               float(self.scale_prior_variance), s, float(self.vae_prior_mean),
+                               self.vae_prior_log_variance, w6, hid3, gw8 if learned else [],
+                               [ghid[0], ghid[1]] if learned else [], *tail)
             gemm([z[cur]], [vw["generative_1"]], [d1], G, G1, Z, Z, G1, G1, epi=EPI_SOFTPLUS,
                  bias=[vb["generative_1"]])
             gemm([d1], [vw["generative_2"]], [d2], G, G2, G1, G1, G2, G2, epi=EPI_SOFTPLUS,

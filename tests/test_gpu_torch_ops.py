@@ -343,6 +343,80 @@ def test_ops_validate_operands():
                       False, 0, 0.0, 1)
 
 
+def test_asr_step_ops_validate_scale_prior_operands():
+    """asr_step_forward_ / asr_step_backward_ take the scale prior as a list:
+    gw=[] (the constant prior: hid / dpre of 8, douts of 12 columns) or the 8
+    gen_scale tensors (hid / dpre of 10, douts of 14 columns).  A list of
+    another length, or hid / douts of the other mode's size, raises before any
+    launch (the outputs keep their NaN fill); a correct call then succeeds on
+    the same buffers in each mode.  B = 4: one workgroup of the step kernels
+    (64 hidden units and the 258 = H + 2 input rows are fixed by them)."""
+    ops = torch.ops.mog_air
+    B = 4
+    g = torch.Generator(device="cpu").manual_seed(5)
+
+    def rn(*s):
+        return (0.1 * torch.randn(*s, generator=g)).to(DEV)
+
+    def nan(*s):
+        return torch.full(s, float("nan"), device=DEV)
+
+    def pair(k, n):  # a dense layer's W [in, out], b
+        return [rn(k, n), rn(n)]
+
+    w20 = (pair(64, 2) + pair(64, 2) + pair(258, 64) + pair(66, 1) + pair(258, 64) + pair(66, 1)
+           + pair(64, 2) + pair(64, 2) + pair(64, 1) + pair(64, 1))
+    gw8 = pair(258, 64) + pair(66, 1) + pair(258, 64) + pair(66, 1)
+    hid0 = rn(10, B, 64).abs()
+    hid = torch.empty_like(hid0)
+    eps_shift, eps_scale = 10 * rn(B, 2), 10 * rn(B)
+    u = torch.rand(B, generator=g).clamp(0.05, 0.95).to(DEV)
+    stop = torch.zeros(B, device=DEV)
+    digits = torch.zeros(B, device=DEV, dtype=torch.int32)
+    live = torch.tensor([1, 0], device=DEV, dtype=torch.int32)
+    rec = nan(30, B)
+    outs = [nan(B, 6), nan(B, 6), nan(B, 3), nan(B), nan(B, 2), nan(B), nan(B), nan(B), nan(B)]
+
+    def forward(gw, nh):
+        ops.asr_step_forward_(B, 0, True, -1, 0.9, 0.1, 0.0, 0.05, float(np.log(0.05)), 1.0, w20,
+                              gw, list(hid[:nh]), eps_shift, eps_scale, u, stop, digits, live, rec,
+                              *outs)
+
+    douts, dpre = {12: nan(B, 12), 14: nan(B, 14)}, nan(10, B, 64)
+    dth_f, dth_b, dot, dreg = rn(B, 6), rn(B, 6), rn(B), rn(4, B)
+
+    def backward(gw, nh, nd):
+        ops.asr_step_backward_(B, True, -1, 0.1, 0.0, 0.05, 1.0 / B, w20, gw, list(hid[:nh]), rec,
+                               eps_shift, eps_scale, dth_f, dth_b, dot, dreg, None,
+                               douts[nd], list(dpre[:nh]))
+
+    hid.copy_(hid0)
+    with pytest.raises(RuntimeError, match="0 or 8 gen_scale"):
+        forward(gw8[:7], 10)
+    with pytest.raises(RuntimeError, match="hidden layers"):
+        forward(gw8, 8)
+    with pytest.raises(RuntimeError, match="hidden layers"):
+        forward([], 10)
+    with pytest.raises(RuntimeError, match="touches"):
+        backward(gw8, 10, 12)
+    torch.cuda.synchronize()
+    assert torch.equal(hid, hid0) and not stop.any() and int(live[1]) == 0
+    for t in [rec, douts[12], douts[14], dpre] + outs:
+        assert torch.isnan(t).all()
+
+    for gw, nh, nd in (([], 8, 12), (gw8, 10, 14)):
+        hid.copy_(hid0)
+        rec.fill_(float("nan"))
+        forward(gw, nh)
+        backward(gw, nh, nd)
+        torch.cuda.synchronize()
+        # record slots 28 / 29 belong to the learned prior
+        assert torch.isfinite(rec[:28]).all() and bool(torch.isfinite(rec[28:]).all()) == (nh == 10)
+        assert torch.isfinite(douts[nd]).all()
+        assert torch.isfinite(dpre[:nh]).all() and all(torch.isfinite(t).all() for t in outs)
+        assert not torch.equal(hid[6:nh], hid0[6:nh])  # finished in place
+
+
 def test_opcheck_launch_level_ops():
     """torch.library.opcheck on launch-level ops: the schemas' (x!)
     annotations match what the kernels write (test_schema) and the ops

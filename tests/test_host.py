@@ -94,8 +94,12 @@ def test_torch_ops_extension_registers_every_launch_op():
                "vae_sample_backward_": {"dmu", "dlv", "dmu_bf16", "dlv_bf16"},
                "recon_loss_": {"canvas", "recon", "bce", "mse", "loss", "acc", "dcanvas"},
                "clip_adam_": {"params", "grads", "m", "v", "sumsq"},
-               "asr_step_forward_": {"hid", "stop", "digits", "live", "rec"},
-               "asr_step_backward_": {"douts", "dpre"}}
+               "asr_step_forward_": {"hid", "stop", "digits", "live", "rec", "theta_fwd",
+                                     "theta_back", "ss", "scale", "shift", "zprob", "zmask",
+                                     "zval", "zc"},
+               "asr_step_backward_": {"douts", "dpre"},
+               "asr_gen_step_": {"stop", "digits", "live", "ss", "z", "theta_back", "zval",
+                                 "zmask"}}
     for op, args in written.items():
         sch = getattr(torch.ops.mog_air, op).default._schema
         mut = {a.name for a in sch.arguments if a.alias_info is not None and a.alias_info.is_write}
