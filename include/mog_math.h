@@ -11,8 +11,30 @@
  * bit-level statement instead of a tolerance argument, every elementwise
  * transcendental on the hot path is defined HERE, once, with only IEEE
  * add/sub/mul/div/sqrt/fma/rint and bit casts, so the HIP kernels (hipcc) and
- * the C oracle (gcc) produce identical bits.  Accuracy against libm is pinned
- * by tests/test_math_spec.py (<= 2 ulp on the tested ranges).
+ * the C oracle (gcc) produce identical bits: tests/test_gpu_math_spec.py
+ * compares the two compilations bit for bit on the input set below.
+ *
+ * Accuracy against float64 libm is pinned by tests/test_math_spec.py, in ulps
+ * of the float32-rounded reference, on a deterministic input set
+ * (tests/math_spec_cases.py: every exponent x 64 mantissas x both signs, the
+ * specials, +-2 ulps around every branch constant below, 400 001 points over
+ * [-110, 90]).  The bounds are that sweep's maxima rounded up to a quarter
+ * ulp; they bound the set, not every float (an exhaustive scan of
+ * [2^-6, 2^-4) finds log1p at 3.79 ulp):
+ *   exp      1.00 ulp  (0.862 at -71.0325; subnormal results included)
+ *   log      1.75 ulp  (1.677 at 1.281; subnormal arguments included)
+ *   expm1    2.75 ulp  (2.671 at 0.4)
+ *   tanh     2.50 ulp  (2.397 at -0.2105)
+ *   sigmoid  2.25 ulp  (2.156 at -16.6535), on x > -88.72283935546875
+ *   softplus 2.25 ulp  (2.029 at 0.23736973), on x >= 0
+ *   log1p    3.25 ulp  (3.243 at 0.029860657)
+ * By construction, and pinned there as known answers:
+ *   sigmoid(x) is exactly 0 for x <= -88.72283935546875 (exp(-x) is +inf; the
+ *   true value is a subnormal near 2.9e-39) and exactly 1 for
+ *   x >= 16.63553237915039;  tanh(x) is exactly +-1 for |x| > 9.1;
+ *   expm1(-0) and tanh(-0) are +0;  softplus for -13.94 <= x < 0 is
+ *   log(exp(x) + 1) in fp32 as TF evaluates it, cancellation included: within
+ *   2^-22 absolute, not within an ulp bound.
  *
  * Rules for this file: no FP contraction (each function body disables it), no
  * library math except sqrtf/rintf/fmaf/floorf (IEEE-exact on host and device).

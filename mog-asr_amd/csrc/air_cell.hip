@@ -1261,7 +1261,9 @@ extern "C" int mog_fill32_batch(int nbuf, void* const* dst, const long* n, const
     f.n[j] = on ? n[j] : 0;
     f.v[j] = on ? value[j] : 0u;
     if (on) {
-      MOG_CHECK_ARG(dst[j] != nullptr && n[j] >= 0 && (reinterpret_cast<size_t>(dst[j]) & 3) == 0);
+      // (an empty buffer may be a null pointer: nothing of it is touched)
+      MOG_CHECK_ARG(n[j] >= 0 && (dst[j] != nullptr || n[j] == 0) &&
+                    (reinterpret_cast<size_t>(dst[j]) & 3) == 0);
       mx = n[j] > mx ? n[j] : mx;
     }
   }
@@ -1282,7 +1284,7 @@ extern "C" int mog_copy32_batch(int nbuf, void* const* dst, const void* const* s
     f.src[j] = on ? reinterpret_cast<const unsigned*>(src[j]) : nullptr;
     f.n[j] = on ? n[j] : 0;
     if (on) {
-      MOG_CHECK_ARG(dst[j] && src[j] && n[j] >= 0 &&
+      MOG_CHECK_ARG(n[j] >= 0 && ((dst[j] && src[j]) || n[j] == 0) &&
                     ((reinterpret_cast<size_t>(dst[j]) | reinterpret_cast<size_t>(src[j])) & 3) == 0);
       mx = n[j] > mx ? n[j] : mx;
     }
@@ -1299,7 +1301,8 @@ extern "C" int mog_transpose32_batch(int nbuf, float* const* dst, const float* c
   TransBatch f{};
   long mx = 0;
   for (int j = 0; j < nbuf; ++j) {
-    MOG_CHECK_ARG(dst[j] && src[j] && rows[j] >= 0 && cols[j] >= 0);
+    MOG_CHECK_ARG(rows[j] >= 0 && cols[j] >= 0 &&
+                  ((dst[j] && src[j]) || (long)rows[j] * cols[j] == 0));
     f.dst[j] = dst[j]; f.src[j] = src[j]; f.rows[j] = rows[j]; f.cols[j] = cols[j];
     mx = std::max<long>(mx, (long)rows[j] * cols[j]);
   }

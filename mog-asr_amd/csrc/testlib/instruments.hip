@@ -9,7 +9,13 @@
 //
 // mog_lds_poison: every CU's LDS filled with one pattern before a kernel, so
 // that a read of LDS the kernel did not write first shows in its outputs.
+//
+// mog_math_probe: the device compilation of include/mog_math.h and
+// csrc/step_math.h, one function per launch over arrays of arguments, so that
+// tests/test_gpu_math_spec.py can compare its bits with the oracle's (gcc's)
+// at the functions' edges.  It calls the header functions as they are.
 #include "../mog_common.h"
+#include "../step_math.h"
 #include "../../../include/mog_air_test.h"
 
 namespace {
@@ -32,7 +38,55 @@ __global__ __launch_bounds__(256) void lds_poison_kernel(unsigned bits) {
   __syncthreads();
 }
 
+struct ProbeArgs {
+  const float* a[6];
+};
+
+// one thread per element, plain loads and stores
+__global__ __launch_bounds__(256) void math_probe_kernel(int fn, ProbeArgs p, float* y, long n,
+                                                         int K, int ldw) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float r;
+  switch (fn) {
+    case MOG_PROBE_EXP: r = mog_expf(p.a[0][i]); break;
+    case MOG_PROBE_LOG: r = mog_logf(p.a[0][i]); break;
+    case MOG_PROBE_EXPM1: r = mog_expm1f(p.a[0][i]); break;
+    case MOG_PROBE_TANH: r = mog_tanhf(p.a[0][i]); break;
+    case MOG_PROBE_SIGMOID: r = mog_sigmoidf(p.a[0][i]); break;
+    case MOG_PROBE_SOFTPLUS: r = mog_softplusf(p.a[0][i]); break;
+    case MOG_PROBE_LOG1P: r = mog_log1pf(p.a[0][i]); break;
+    case MOG_PROBE_LOGISTIC_NOISE: r = logistic_noise(p.a[0][i]); break;
+    case MOG_PROBE_LSE0: r = lse0(p.a[0][i]); break;
+    case MOG_PROBE_CONCRETE_KL:
+      r = concrete_kl(p.a[0][i], p.a[1][i], p.a[2][i], p.a[3][i], p.a[4][i]);
+      break;
+    case MOG_PROBE_GAUSS_KL_TERM:
+      r = gauss_kl_term(p.a[0][i], p.a[1][i], p.a[2][i], p.a[3][i], p.a[4][i], p.a[5][i]);
+      break;
+    case MOG_PROBE_CHAIN_DOT: r = chain_dot(p.a[0] + (size_t)i * K, p.a[1], K, ldw); break;
+    default: r = chain64(p.a[0] + (size_t)i * 64, p.a[1], ldw); break;  // MOG_PROBE_CHAIN64
+  }
+  y[i] = r;
+}
+
 }  // namespace
+
+extern "C" int mog_math_probe(int fn, const float* const* args, int nargs, float* y, long n,
+                              int K, int ldw, void* stream) {
+  static const int want[MOG_PROBE_COUNT] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 5, 6, 2, 2};
+  MOG_CHECK_ARG(fn >= 0 && fn < MOG_PROBE_COUNT && args && nargs == want[fn] && y && n >= 0);
+  const bool chain = fn == MOG_PROBE_CHAIN_DOT || fn == MOG_PROBE_CHAIN64;
+  MOG_CHECK_ARG(!chain || (K >= 0 && ldw >= 1 && (fn != MOG_PROBE_CHAIN64 || K == 64)));
+  ProbeArgs p{};
+  for (int j = 0; j < nargs; ++j) {
+    MOG_CHECK_ARG(args[j] != nullptr);
+    p.a[j] = args[j];
+  }
+  if (n == 0) return 0;
+  math_probe_kernel<<<mog_cdiv(n, 256), 256, 0, mog_stream(stream)>>>(fn, p, y, n, K, ldw);
+  MOG_LAUNCH_RET();
+}
 
 extern "C" int mog_lds_poison(unsigned bits, void* stream) {
   // 80 KiB per workgroup (two fill a CU's 160 KiB), eight rounds of them

@@ -143,13 +143,15 @@ def load():
 
 # test-only instruments (include/mog_air_test.h): their own library
 TEST_LIB_PATH = os.path.join(_HERE, "_lib", "libmog_air_test.so")
-_TEST_SIGS = {"mog_spin": [LL, P], "mog_lds_poison": [ctypes.c_uint, P]}
+_TEST_SIGS = {"mog_spin": [LL, P], "mog_lds_poison": [ctypes.c_uint, P],
+              "mog_math_probe": [I, P, I, P, L, I, I, P]}
 _test_lib = None
 
 
 def load_test():
-    """libmog_air_test.so (mog_spin, mog_lds_poison): the stream-ordering and
-    LDS-hygiene test instruments, kept out of the product library."""
+    """libmog_air_test.so (mog_spin, mog_lds_poison, mog_math_probe): the
+    stream-ordering, LDS-hygiene and device-numerics test instruments, kept
+    out of the product library."""
     global _test_lib
     if _test_lib is None:
         if not os.path.exists(TEST_LIB_PATH):

@@ -502,3 +502,47 @@ def lds_poison(bits: int = 0x7FC00000) -> None:
     rc = _lib.load_test().mog_lds_poison(int(bits) & 0xFFFFFFFF, stream_ptr())
     if rc != 0:
         raise _lib.MogError(f"mog_lds_poison failed ({rc})")
+
+
+# function ids of mog_math_probe (include/mog_air_test.h); 0..6 are the
+# oracle's oracle_math_vec ids
+PROBE_FNS = ("exp", "log", "expm1", "tanh", "sigmoid", "softplus", "log1p", "logistic_noise",
+             "lse0", "concrete_kl", "gauss_kl_term", "chain_dot", "chain64")
+_PROBE_NARGS = (1, 1, 1, 1, 1, 1, 1, 1, 1, 5, 6, 2, 2)
+
+
+def math_probe(fn, *args: torch.Tensor, K: int = 0, ldw: int = 1) -> torch.Tensor:
+    """One function of include/mog_math.h / csrc/step_math.h as the device
+    compiler builds it, over arrays of arguments (test instrument
+    mog_math_probe of libmog_air_test.so).  `fn`: an id or a name of
+    PROBE_FNS.  Elementwise functions take equally long fp32 vectors.  The
+    chains take a [n, K] and w (K rows of pitch ldw; column 0 is read) and
+    return the n k-ordered fma chains."""
+    fn = PROBE_FNS.index(fn) if isinstance(fn, str) else int(fn)
+    if not 0 <= fn < len(PROBE_FNS) or len(args) != _PROBE_NARGS[fn]:
+        raise ValueError(f"math_probe: function {fn} takes {_PROBE_NARGS[fn]} arrays")
+    for j, t in enumerate(args):
+        _chk(t, f"args[{j}]")
+    if PROBE_FNS[fn] in ("chain_dot", "chain64"):
+        a, w = args
+        if PROBE_FNS[fn] == "chain64":
+            K = 64
+        if a.dim() != 2 or a.shape[1] != K or K < 0 or ldw < 1:
+            raise ValueError("math_probe: a must be [n, K], ldw >= 1")
+        if w.numel() < (0 if K == 0 else (K - 1) * ldw + 1):
+            raise ValueError("math_probe: w holds fewer than (K - 1) ldw + 1 elements")
+        n = a.shape[0]
+    else:
+        n = args[0].numel()
+        if any(t.numel() != n for t in args):
+            raise ValueError("math_probe: argument arrays differ in length")
+    y = torch.empty(n, device=args[0].device, dtype=torch.float32)
+    if n == 0:
+        return y
+    # (K == 0: a and w hold nothing and have null data_ptrs; never read)
+    ptrs = _lib.ptr_array([t.data_ptr() or y.data_ptr() for t in args])
+    rc = _lib.load_test().mog_math_probe(fn, ptrs, len(args), y.data_ptr(), n, int(K), int(ldw),
+                                         stream_ptr())
+    if rc != 0:
+        raise _lib.MogError(f"mog_math_probe failed ({rc})")
+    return y

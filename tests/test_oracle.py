@@ -28,7 +28,9 @@ def _ulp_err(got, ref):
     (2, -10.0, 10.0, np.expm1, 3.0),
     (3, -10.0, 10.0, np.tanh, 3.0),
     (4, -30.0, 30.0, lambda x: 1.0 / (1.0 + np.exp(-x)), 3.0),
-    (6, 0.0, 1.0, np.log1p, 3.0),
+    # log1p: the bound of the deterministic sweep (tests/test_math_spec.py,
+    # 3.24 ulp at 0.029860657, inside this range; this random sample misses it)
+    (6, 0.0, 1.0, np.log1p, 3.25),
 ])
 def test_math_spec_vs_libm(fn, lo, hi, ref, tol):
     lib = ao._load()
