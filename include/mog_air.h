@@ -674,6 +674,22 @@ int mog_eval_detection_means(const double* per_image, int N, double* means, void
 int mog_gather_rows(const float* src, const int* ksrc, const int* idx, int rows, int width,
                     int B, float* out, int* kout, void* stream);
 
+/* ---- training canvases made on the device ------------------
+ * Images first .. first + b - 1 of stream `seed`, each a pure function of
+ * (seed, image number): glyphs of `bank` [G][32][32] (fp32, top-left aligned,
+ * zero padded; sizes [G][2] = (h, w), 1 <= h, w <= min(32, C)) placed without
+ * pixel overlap on a C x C canvas (32 <= C <= 64) as
+ * datasets.generate_multi_image places them, the draws taken from
+ * Philox4x32-10 words (csrc/synth.hip states the definition).  The object
+ * count is counts[pick] (ncounts values in 0..8).  images [b][C*C] in [0, 1],
+ * digits [b] the objects placed, objects [b][8][5] = (glyph, x, y, w, h) with
+ * -1 rows past digits, status [b] = 1 where 8 restarts found no layout (the
+ * image then holds fewer objects than drawn, digits says how many).  One
+ * launch, no atomics, no host synchronisation; first + b <= 2^52. */
+int mog_synth_canvases(const float* bank, const int* sizes, int G, const int* counts, int ncounts,
+                       int C, unsigned long long seed, unsigned long long first, int b,
+                       float* images, int* digits, int* objects, int* status, void* stream);
+
 /* ---- measurement instrument (no reference counterpart) -------------------
  * dst[i] = src[i] for n4 float4s (16-byte aligned): the copy bandwidth the
  * bench quotes beside the HBM spec.  (The test-only instruments mog_spin and

@@ -15,6 +15,23 @@ __device__ __forceinline__ void mog_philox_round(uint32_t c[4], uint32_t k0, uin
   c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
 }
 
+// the four raw 32-bit words for counter {lo32(ctr), hi32(ctr), tag, 0}.  The
+// models' noise (mog_philox_quad) has tag 0; a stream with a non-zero tag never
+// shares a counter with it, whatever the seeds (synth.hip).
+__device__ __forceinline__ void mog_philox_words(uint64_t seed, uint64_t ctr, uint32_t tag,
+                                                 uint32_t w[4]) {
+  uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), tag, 0u};
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    mog_philox_round(c, k0, k1);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) w[k] = c[k];
+}
+
 // four values for counter `ctr`: standard normals (Box-Muller) or U[0,1)
 __device__ __forceinline__ void mog_philox_quad(uint64_t seed, uint64_t ctr, bool normal,
                                                 float v[4]) {

@@ -422,6 +422,26 @@ void gather_rows_(const Tensor& src, const optional<Tensor>& ksrc, const Tensor&
   check(mog_gather_rows(ps, pks, pi, (int)rows, (int)width, (int)B, po, pko, o.stream()), o.name);
 }
 
+// training canvases made on the device (mog_synth_canvases)
+void synth_canvases_(const Tensor& bank, const Tensor& sizes, int64_t G, const Tensor& counts,
+                     int64_t ncounts, int64_t C, int64_t seed, int64_t first, int64_t b,
+                     Tensor images, Tensor digits, Tensor objects, Tensor status) {
+  Op o("synth_canvases_");
+  TORCH_CHECK(G >= 1 && ncounts >= 1 && C >= 32 && C <= 64 && b >= 0 && first >= 0, o.name,
+              ": bad extents (G, ncounts >= 1; 32 <= C <= 64; b, first >= 0)");
+  float* pi = o.f(images, b * C * C, "images");
+  int* pd = o.i(digits, b, "digits");
+  int* po = o.i(objects, b * 8 * 5, "objects");
+  int* ps = o.i(status, b, "status");
+  float* pb = o.f(bank, G * 32 * 32, "bank");
+  int* pz = o.i(sizes, G * 2, "sizes");
+  int* pc = o.i(counts, ncounts, "counts");
+  GUARD(o);
+  check(mog_synth_canvases(pb, pz, (int)G, pc, (int)ncounts, (int)C, (unsigned long long)seed,
+                           (unsigned long long)first, (int)b, pi, pd, po, ps, o.stream()),
+        o.name);
+}
+
 // ----------------------------------------------------------------- LSTM ----
 void lstm_cell_forward_(const Tensor& G, const optional<Tensor>& bias,
                         const optional<Tensor>& c_prev, Tensor c_out, Tensor h_out, int64_t B,
@@ -1663,6 +1683,10 @@ TORCH_LIBRARY_FRAGMENT(mog_air, m) {
       "gather_rows_(Tensor src, Tensor? ksrc, Tensor idx, int rows, int width, int B, "
       "Tensor(a!) out, Tensor(b!)? kout) -> ()");
   m.def(
+      "synth_canvases_(Tensor bank, Tensor sizes, int G, Tensor counts, int ncounts, int C, "
+      "int seed, int first, int b, Tensor(a!) images, Tensor(b!) digits, Tensor(c!) objects, "
+      "Tensor(d!) status) -> ()");
+  m.def(
       "asr_terms_(int B, int T, int C, int[] cons, float[] gammas, Tensor rec, Tensor vkl, "
       "Tensor zmask, Tensor live, Tensor(a!) klsum, Tensor(b!) pr, Tensor(c!) area, "
       "Tensor(d!) out, Tensor(e!) size, Tensor(f!) overlap, Tensor(g!) zsum) -> ()");
@@ -1737,6 +1761,7 @@ TORCH_LIBRARY_IMPL(mog_air, CUDA, m) {
   m.impl("eval_detection_", &eval_detection_);
   m.impl("eval_detection_means_", &eval_detection_means_);
   m.impl("gather_rows_", &gather_rows_);
+  m.impl("synth_canvases_", &synth_canvases_);
   m.impl("asr_terms_", &asr_terms_);
   m.impl("asr_finalize_", &asr_finalize_);
   m.impl("asr_terms_backward_", &asr_terms_backward_);

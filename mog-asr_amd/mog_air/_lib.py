@@ -99,6 +99,7 @@ _SIGS = {
     "mog_eval_detection": [P, P, I, P, P, I, L, L, L, L, P, I, I, I, ctypes.c_double, P, P, I, P],
     "mog_eval_detection_means": [P, I, P, P],
     "mog_gather_rows": [P, P, P, I, I, I, P, P, P],
+    "mog_synth_canvases": [P, P, I, P, I, I, ULL, ULL, I, P, P, P, P, P],
 }
 
 # entry points that do not return an int status

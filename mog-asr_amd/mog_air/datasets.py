@@ -102,6 +102,45 @@ def generate_multi_image(glyphs: Sequence[np.ndarray], num: int, canvas: int,
             return np.clip(img, 0.0, 1.0), ids, pos, box
 
 
+def _glyph_source(kind: str, rng: np.random.Generator, bbox: bool,
+                  dsprites_npz: Optional[str]):
+    """(glyphs, labels, canvas size) of a stand-in dataset: the first draws
+    ``synthesize`` takes from its generator."""
+    if kind == "mnist":
+        lo, hi = (11, 15) if bbox else (17, 23)
+        glyphs = stroke_glyphs(512, rng, lo, hi)
+        labels = rng.integers(0, 10, len(glyphs))
+        return glyphs, labels, 50
+    path = dsprites_npz or os.path.join("data", "multi_dsprites", "data.npz")
+    if not os.path.exists(path):  # the copy shipped with this repository
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "data",
+                            "multi_dsprites", "data.npz")
+    glyphs, lab = dsprite_glyphs(path)
+    return glyphs, (lab[:, 1] if lab.ndim == 2 else lab), 64
+
+
+BANK_SIDE = 32
+
+
+def glyph_bank(kind: str, bbox: bool = False, seed: int = 0,
+               dsprites_npz: Optional[str] = None):
+    """The glyphs ``synthesize(kind, ..., seed, bbox)`` places, as the device
+    generator reads them (ops.synth_canvases): bank [G, 32, 32] float32, every
+    glyph after ``crop_non_empty``, top-left aligned and zero padded; sizes
+    [G, 2] int32 = (h, w); labels [G]."""
+    glyphs, labels, _ = _glyph_source(kind, np.random.default_rng(seed), bbox, dsprites_npz)
+    bank = np.zeros((len(glyphs), BANK_SIDE, BANK_SIDE), np.float32)
+    sizes = np.zeros((len(glyphs), 2), np.int32)
+    for i, glyph in enumerate(glyphs):
+        g = crop_non_empty(glyph)
+        h, w = g.shape
+        if h > BANK_SIDE or w > BANK_SIDE:
+            raise ValueError(f"glyph {i} is {h} x {w}: the bank holds {BANK_SIDE} x {BANK_SIDE}")
+        bank[i, :h, :w] = g
+        sizes[i] = (h, w)
+    return bank, sizes, np.asarray(labels)
+
+
 def synthesize(kind: str, num_in_common: Sequence[int], images_per_count: int,
                test_set_size: int, seed: int = 0, bbox: bool = False,
                dsprites_npz: Optional[str] = None) -> Dict[str, Dict[str, list]]:
@@ -110,19 +149,7 @@ def synthesize(kind: str, num_in_common: Sequence[int], images_per_count: int,
     shuffled together, the first ``test_set_size`` forming the test split
     (multi_mnist.py:489-555)."""
     rng = np.random.default_rng(seed)
-    if kind == "mnist":
-        lo, hi = (11, 15) if bbox else (17, 23)
-        glyphs = stroke_glyphs(512, rng, lo, hi)
-        labels = rng.integers(0, 10, len(glyphs))
-        canvas = 50
-    else:
-        path = dsprites_npz or os.path.join("data", "multi_dsprites", "data.npz")
-        if not os.path.exists(path):  # the copy shipped with this repository
-            path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "data",
-                                "multi_dsprites", "data.npz")
-        glyphs, lab = dsprite_glyphs(path)
-        labels = lab[:, 1] if lab.ndim == 2 else lab
-        canvas = 64
+    glyphs, labels, canvas = _glyph_source(kind, rng, bbox, dsprites_npz)
     order: List[int] = []
     rows = []
     for n in num_in_common:

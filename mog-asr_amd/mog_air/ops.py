@@ -475,6 +475,83 @@ def gather_rows(src: torch.Tensor, idx, out: torch.Tensor, ksrc: Optional[torch.
     _ops.gather_rows_(src, ksrc, dev_idx, rows, width, B, out, kout)
 
 
+SYNTH_SIDE, SYNTH_GMAX, SYNTH_MAX_INDEX = 32, 8, 2 ** 52
+
+
+class SynthBank:
+    """A glyph bank for ``synth_canvases``, checked once on the host and held
+    on the device: bank [G, 32, 32] float32 (glyphs top-left aligned, zero
+    padded), sizes [G, 2] int32 (h, w) and the object counts to draw from,
+    for canvases of ``canvas`` x ``canvas`` pixels.  Everything that bounds a
+    loop or an address of the kernel is refused here (ValueError): a bank side
+    other than 32, h or w outside 1..min(32, canvas), a canvas outside 32..64,
+    a count outside 0..8, an empty bank or count list, wrongly typed or
+    non-contiguous arrays."""
+
+    def __init__(self, bank, sizes, counts, canvas: int, device):
+        import numpy as np
+        for a, name, dt in ((bank, "bank", np.float32), (sizes, "sizes", np.int32)):
+            if not isinstance(a, np.ndarray) or a.dtype != dt:
+                raise ValueError(f"{name} must be a host array of {np.dtype(dt).name}")
+            if not a.flags["C_CONTIGUOUS"]:
+                raise ValueError(f"{name} must be contiguous")
+        if bank.ndim != 3 or bank.shape[0] < 1 or bank.shape[1:] != (SYNTH_SIDE, SYNTH_SIDE):
+            raise ValueError(f"bank must be [G >= 1, {SYNTH_SIDE}, {SYNTH_SIDE}], got "
+                             f"{bank.shape}")
+        if sizes.shape != (bank.shape[0], 2):
+            raise ValueError(f"sizes must be [{bank.shape[0]}, 2], got {sizes.shape}")
+        canvas = int(canvas)
+        if not SYNTH_SIDE <= canvas <= 64:
+            raise ValueError(f"canvas {canvas} outside {SYNTH_SIDE}..64")
+        if sizes.min() < 1 or sizes.max() > min(SYNTH_SIDE, canvas):
+            raise ValueError(f"glyph sides outside 1..{min(SYNTH_SIDE, canvas)}")
+        counts = np.asarray(counts)
+        if counts.ndim != 1 or counts.size < 1 or counts.dtype.kind not in "iu":
+            raise ValueError("counts must be a non-empty list of integers")
+        if counts.min() < 0 or counts.max() > SYNTH_GMAX:
+            raise ValueError(f"object counts outside 0..{SYNTH_GMAX}")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("the bank lives on a HIP device")
+        self.canvas, self.G = canvas, int(bank.shape[0])
+        self.bank = torch.from_numpy(bank).to(dev)
+        self.sizes = torch.from_numpy(sizes).to(dev)
+        self.counts = torch.from_numpy(counts.astype(np.int32)).to(dev)
+
+
+def synth_canvases(sbank: SynthBank, seed: int, first: int, images: torch.Tensor,
+                   digits: torch.Tensor, objects: torch.Tensor, status: torch.Tensor) -> None:
+    """Images first .. first + b - 1 of stream `seed` (mog_synth_canvases; b =
+    the rows of `images`): images [b, C*C] float32, digits [b], objects
+    [b, 8, 5] = (glyph, x, y, w, h), -1 past digits, and status [b], int32.
+    One launch on the current stream, no host synchronisation.  A wrong shape,
+    dtype or device, or an image number at or beyond 2^52, raises ValueError
+    before any launch."""
+    if not isinstance(sbank, SynthBank):
+        raise ValueError("sbank must be an ops.SynthBank")
+    _chk(images, "images")
+    for t, name in ((digits, "digits"), (objects, "objects"), (status, "status")):
+        _chk(t, name, torch.int32)
+    C = sbank.canvas
+    if images.dim() != 2 or images.shape[1] != C * C:
+        raise ValueError(f"images must be [b, {C * C}], got {tuple(images.shape)}")
+    b = images.shape[0]
+    if tuple(digits.shape) != (b,) or tuple(status.shape) != (b,) or \
+            tuple(objects.shape) != (b, SYNTH_GMAX, 5):
+        raise ValueError(f"digits and status must be [{b}] and objects [{b}, {SYNTH_GMAX}, 5]")
+    for t, name in ((images, "images"), (digits, "digits"), (objects, "objects"),
+                    (status, "status")):
+        if t.device != sbank.bank.device:
+            raise ValueError(f"{name} is on {t.device}, the bank on {sbank.bank.device}")
+    seed, first = int(seed), int(first)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be an unsigned 64-bit integer")
+    if first < 0 or first + b > SYNTH_MAX_INDEX:
+        raise ValueError(f"images [{first}, {first + b}) outside [0, 2^52)")
+    _ops.synth_canvases_(sbank.bank, sbank.sizes, sbank.G, sbank.counts, sbank.counts.numel(), C,
+                         _i64(seed), first, b, images, digits, objects, status)
+
+
 def _i64(v: int) -> int:
     """a 64-bit counter / seed as the signed int64 of an op schema's `int`"""
     v &= 2 ** 64 - 1

@@ -416,3 +416,76 @@ class DeviceFeed:
 
     def fingerprint(self):
         return self._picks.fingerprint()
+
+
+class StreamFeed:
+    """Training canvases made on the device, as many fresh ones per step as
+    the step wants (ops.synth_canvases): global batch i is
+    images i * batch_size .. of stream ``seed``, each a pure function of
+    (seed, image number), so the batches do not depend on the number of ranks
+    and a restored run continues bit for bit.  ``next_batch`` returns this
+    rank's contiguous shard (parallel.shard) as fresh device tensors (x
+    [b, C*C] float32, k [b] int32) and the global batch size; only the shard's
+    images are generated.  ``objects`` [b, 8, 5] = (glyph, x, y, w, h) and
+    ``status`` [b] are those of the last batch.  The stream never ends.
+
+    ``bank`` / ``sizes``: datasets.glyph_bank; ``counts``: the object counts to
+    draw from.  No device is touched before the first ``next_batch``."""
+
+    def __init__(self, bank: np.ndarray, sizes: np.ndarray, counts, canvas: int, batch_size: int,
+                 seed: int = 12345, device="cuda:0", rank: int = 0, world: int = 1):
+        if batch_size < 1:
+            raise ValueError("batch_size must be positive")
+        self._bank = np.ascontiguousarray(bank, np.float32)
+        self._sizes = np.ascontiguousarray(sizes, np.int32)
+        self._counts = np.asarray(counts, np.int64).reshape(-1)
+        self.canvas, self.batch_size, self.seed = int(canvas), int(batch_size), int(seed)
+        self.device, self.rank, self.world = device, int(rank), int(world)
+        self._next = 0
+        self._sbank = None
+        self.objects = self.status = None
+
+    def _shard(self):
+        # (parallel.shard restated: this module imports without torch)
+        base, extra = divmod(self.batch_size, self.world)
+        lo = self.rank * base + min(self.rank, extra)
+        return lo, lo + base + (1 if self.rank < extra else 0)
+
+    def next_batch(self):
+        import torch
+
+        from . import ops
+        if self._sbank is None:
+            self._sbank = ops.SynthBank(self._bank, self._sizes, self._counts, self.canvas,
+                                        self.device)
+        dev = self._sbank.bank.device
+        lo, hi = self._shard()
+        b = hi - lo
+        x = torch.empty((b, self.canvas * self.canvas), dtype=torch.float32, device=dev)
+        k = torch.empty((b,), dtype=torch.int32, device=dev)
+        self.objects = torch.empty((b, ops.SYNTH_GMAX, 5), dtype=torch.int32, device=dev)
+        self.status = torch.empty((b,), dtype=torch.int32, device=dev)
+        ops.synth_canvases(self._sbank, self.seed, self._next + lo, x, k, self.objects,
+                           self.status)
+        self._next += self.batch_size
+        return x, k, self.batch_size
+
+    def get_state(self) -> Dict[str, object]:
+        """The number of the next global batch's first image (``buf``: the
+        empty array checkpoint.save_state stores for every feed)."""
+        return {"kind": "stream", "next": int(self._next), "buf": np.zeros((0,), np.int64)}
+
+    def set_state(self, state) -> None:
+        if state.get("kind") != "stream":
+            raise ValueError("not the state of a stream feed: %r" % sorted(state))
+        nxt = int(state["next"])
+        if nxt < 0:
+            raise ValueError("feed state points before the stream's first image")
+        self._next = nxt
+
+    def fingerprint(self) -> Dict[str, object]:
+        """What a saved stream position is only valid for."""
+        return {"stream_seed": self.seed, "canvas": self.canvas,
+                "counts": [int(c) for c in self._counts], "glyphs": int(len(self._bank)),
+                "bank_crc32": int(zlib.crc32(self._bank.tobytes()) ^
+                                  zlib.crc32(self._sizes.tobytes()))}

@@ -46,7 +46,7 @@ def add_common_args(parser, reader_threads: int):
     train_air_pr.py:40-61) plus this framework's options (not in the
     reference): --iterations, --precision, --test-batch, --synth-per-count,
     --write-synthetic, --device, --resident, --save-every, --restore,
-    --restore-mode, --eval-only."""
+    --restore-mode, --eval-only, --batch-size, --stream, --stream-seed."""
     parser.add_argument("-r", "--results-folder", default="Not Valid")
     parser.add_argument("-k", "-key", "--key", default="")
     parser.add_argument("-gpu", "--gpu", default="-1")
@@ -83,6 +83,12 @@ def add_common_args(parser, reader_threads: int):
     parser.add_argument("--eval-only", type=int, choices=[0, 1], default=0,
                         help="1 (with --restore): the final test pass and grids of the restored "
                              "state, no training")
+    parser.add_argument("--batch-size", type=int, default=BATCH_SIZE,
+                        help="images per train step, over all ranks (the reference's 64)")
+    parser.add_argument("--stream", type=int, choices=[0, 1], default=0,
+                        help="1: every batch is fresh stand-in canvases made on the device "
+                             "(records.StreamFeed); needs --iterations and absent dataset files")
+    parser.add_argument("--stream-seed", type=int, default=12345)
 
 
 def select_gpu(gpu: str) -> None:
@@ -170,6 +176,24 @@ def dataset_files(args, entry: str):
         folder, canvas = "./data/multi_dsprites/", 64
     return (os.path.join(folder, f"common{name}.tfrecords"),
             os.path.join(folder, f"test{name}.tfrecords"), canvas, name, digits)
+
+
+def check_feed_args(args, train_file: str, test_file: str) -> None:
+    """--batch-size / --stream: refused before anything is written.  A stream
+    of stand-in glyphs is not mixed with a real test file, and it never ends,
+    so the run needs --iterations."""
+    if getattr(args, "batch_size", BATCH_SIZE) < 1:
+        raise ValueError("--batch-size must be positive")
+    if not getattr(args, "stream", 0):
+        return
+    if os.path.exists(train_file) or os.path.exists(test_file):
+        raise ValueError("--stream 1 draws the offline stand-in glyphs, but the dataset files "
+                         "%s / %s exist: train from them (--stream 0) or move them away" % (
+                             train_file, test_file))
+    if not args.iterations > 0:
+        raise ValueError("--stream 1 needs --iterations: the stream never ends")
+    if not 0 <= args.stream_seed < 2 ** 63:
+        raise ValueError("--stream-seed must be in [0, 2^63)")
 
 
 def results_folder(args, entry: str, name: str, main: bool = True) -> str:
@@ -375,9 +399,9 @@ def resident_ok(args, tr_x, test, test_model, log) -> bool:
 class _HostFeed:
     """The host input pipeline: ShuffleBatcher batches, sharded per rank."""
 
-    def __init__(self, tr_x, tr_k, ctx):
+    def __init__(self, tr_x, tr_k, ctx, batch_size: int = BATCH_SIZE):
         self.ctx = ctx
-        self.batcher = records.ShuffleBatcher(tr_x, tr_k, BATCH_SIZE, EPOCHS,
+        self.batcher = records.ShuffleBatcher(tr_x, tr_k, batch_size, EPOCHS,
                                               min_after_dequeue=min(10000, len(tr_k)))
 
     def next_batch(self):
@@ -396,12 +420,29 @@ class _HostFeed:
         return self.batcher.fingerprint()
 
 
+def stream_feed(args, ctx, batch_size: int):
+    """records.StreamFeed over the glyphs load_data's stand-in test set was
+    made from (datasets.synthesize with seed 0), on -data's canvas, drawing the
+    object counts of -dn."""
+    from . import datasets
+    kind = "mnist" if args.data.lower() == "mnist" else "dsprites"
+    bank, sizes, _ = datasets.glyph_bank(kind, bbox="bbox" in args.dig_surfix, seed=0)
+    return records.StreamFeed(bank, sizes, [int(c) for c in args.dig_num],
+                              50 if kind == "mnist" else 64, batch_size,
+                              seed=getattr(args, "stream_seed", 12345), device=args.device,
+                              rank=ctx.rank, world=ctx.world)
+
+
 def make_feed(args, tr_x, tr_k, ctx, resident: bool):
     """(x, k, global batch size) per ``next_batch()``: this rank's shard of
-    the shuffled batch, host arrays or (resident) device tensors."""
+    the shuffled batch, host arrays or (resident) device tensors; with
+    --stream 1 fresh canvases made on the device (the train split is unused)."""
+    batch_size = getattr(args, "batch_size", BATCH_SIZE)
+    if getattr(args, "stream", 0):
+        return stream_feed(args, ctx, batch_size)
     if not resident:
-        return _HostFeed(tr_x, tr_k, ctx)
-    return records.DeviceFeed(tr_x, tr_k, BATCH_SIZE, EPOCHS,
+        return _HostFeed(tr_x, tr_k, ctx, batch_size)
+    return records.DeviceFeed(tr_x, tr_k, batch_size, EPOCHS,
                               min_after_dequeue=min(10000, len(tr_k)), device=args.device,
                               rank=ctx.rank, world=ctx.world)
 

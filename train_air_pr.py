@@ -55,6 +55,7 @@ def main(argv=None):
     else:
         size_min, size_max = (12, 15) if "bbox" in args.dig_surfix else (20, 25)
     print(size_min, size_max)
+    trainer.check_feed_args(args, train_file, test_file)
     ctx = trainer.distributed_setup(args)  # one process per GPU under torch.distributed.run
     folder = trainer.results_folder(args, "train_air_pr.py", name, main=ctx.main)
     log = trainer.build_logger(folder, args, main=ctx.main)

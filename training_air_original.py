@@ -41,6 +41,7 @@ def main(argv=None):
     from mog_air.air_model import AIRModel
 
     train_file, test_file, canvas, name, digits = trainer.dataset_files(args, "training_air_original.py")
+    trainer.check_feed_args(args, train_file, test_file)
     ctx = trainer.distributed_setup(args)  # one process per GPU under torch.distributed.run
     folder = trainer.results_folder(args, "training_air_original.py", name, main=ctx.main)
     log = trainer.build_logger(folder, args, main=ctx.main)
