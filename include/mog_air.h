@@ -690,6 +690,26 @@ int mog_synth_canvases(const float* bank, const int* sizes, int G, const int* co
                        int C, unsigned long long seed, unsigned long long first, int b,
                        float* images, int* digits, int* objects, int* status, void* stream);
 
+/* ---- the AIR-ASR log row of one step -----------------------
+ * out[16] = the model's log_variables of the step whose workspace arrays are
+ * given, in the property's order (z_pres_kl, scale_kl, shift_kl, vae_kl,
+ * pr_num, recon, mse, area_loss, out_loss, size_loss, over_loss, num_margin,
+ * num_min_KL, TotLoss, elbo, accu), in one launch of one workgroup.  With
+ * T_exec = sum of live[0:T] (int32 flags): the four record sums are
+ * (1/B) sum_b sum_{t < T_exec} arec[t][slot][b] for the slots q[0..3] (zkl,
+ * skl, shkl, prn) of arec [T][NQ][B]; vae_kl likewise over the fp32 product
+ * vkl[t][b] zmask[t][b]; recon .. num_min_KL the batch means of bce, mse,
+ * area, outl, size, over, element [B]; elbo the batch mean of the fp32 sum
+ * klsum[b] + bce[b]; num_margin, TotLoss, accu the bits of margin[0],
+ * means[0], means[1].  Sums run in float64 in an order fixed by (B, T_exec)
+ * (no atomics: the same bits on every launch), are divided in float64 and
+ * rounded once to fp32; rows t >= T_exec are not read.  1 <= T <= 8. */
+int mog_asr_log_row(const float* arec, int NQ, const int* q, const float* vkl,
+                    const float* zmask, const int* live, const float* bce, const float* mse,
+                    const float* area, const float* outl, const float* size, const float* over,
+                    const float* element, const float* klsum, const float* margin,
+                    const float* means, int T, int B, float* out, void* stream);
+
 /* ---- measurement instrument (no reference counterpart) -------------------
  * dst[i] = src[i] for n4 float4s (16-byte aligned): the copy bandwidth the
  * bench quotes beside the HBM spec.  (The test-only instruments mog_spin and

@@ -1291,6 +1291,40 @@ void asr_step_backward_(int64_t B, bool train, int64_t fix_steps, double tempera
         o.name);
 }
 
+// the AIR-ASR log row of the last step (mog_asr_log_row): arec [T, NQ, B], vkl /
+// zmask [T, B], live int32 [>= T], the per-image arrays [B], margin [1],
+// means [4], out [16]
+void asr_log_row_(int64_t B, int64_t T, at::IntArrayRef slots, const Tensor& arec,
+                  const Tensor& vkl, const Tensor& zmask, const Tensor& live, const Tensor& bce,
+                  const Tensor& mse, const Tensor& area, const Tensor& outl, const Tensor& size,
+                  const Tensor& over, const Tensor& element, const Tensor& klsum,
+                  const Tensor& margin, const Tensor& means, Tensor out) {
+  Op o("asr_log_row_");
+  TORCH_CHECK(B >= 1 && B <= INT32_MAX && T >= 1 && T <= 8, o.name, ": B >= 1, T in 1..8");
+  TORCH_CHECK(slots.size() == 4, o.name, ": 4 record slots (zkl, skl, shkl, prn)");
+  vector<int> q(slots.begin(), slots.end());
+  for (int v : q) TORCH_CHECK(v >= 0 && v < ASR_NQ, o.name, ": record slot outside 0..", ASR_NQ - 1);
+  float* po = o.f(out, 16, "out");
+  float* pr = o.f(arec, T * ASR_NQ * B, "arec");
+  float* pv = o.f(vkl, T * B, "vkl");
+  float* pz = o.f(zmask, T * B, "zmask");
+  const int* pl = o.i(live, T, "live");
+  float* pb = o.f(bce, B, "bce");
+  float* pm = o.f(mse, B, "mse");
+  float* pa = o.f(area, B, "area");
+  float* pol = o.f(outl, B, "outl");
+  float* ps = o.f(size, B, "size");
+  float* pov = o.f(over, B, "over");
+  float* pe = o.f(element, B, "element");
+  float* pk = o.f(klsum, B, "klsum");
+  float* pmg = o.f(margin, 1, "margin");
+  float* pmn = o.f(means, 4, "means");
+  GUARD(o);
+  check(mog_asr_log_row(pr, (int)ASR_NQ, q.data(), pv, pz, pl, pb, pm, pa, pol, ps, pov, pe, pk,
+                        pmg, pmn, (int)T, (int)B, po, o.stream()),
+        o.name);
+}
+
 }  // namespace
 
 // split-K partials of the TN forms: reduce = 1 -> a transient [splitk][M][N]
@@ -1702,6 +1736,10 @@ TORCH_LIBRARY_FRAGMENT(mog_air, m) {
       "float s_pv, float grad_scale, Tensor[] w, Tensor[] gw, Tensor?[] hid, Tensor rec, "
       "Tensor eps_shift, Tensor eps_scale, Tensor dtheta_fwd, Tensor dtheta_back, Tensor dot, "
       "Tensor dreg, Tensor? dss, Tensor(a!) douts, Tensor(b!)?[] dpre) -> ()");
+  m.def(
+      "asr_log_row_(int B, int T, int[] slots, Tensor arec, Tensor vkl, Tensor zmask, "
+      "Tensor live, Tensor bce, Tensor mse, Tensor area, Tensor outl, Tensor size, Tensor over, "
+      "Tensor element, Tensor klsum, Tensor margin, Tensor means, Tensor(a!) out) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(mog_air, CUDA, m) {
@@ -1766,4 +1804,5 @@ TORCH_LIBRARY_IMPL(mog_air, CUDA, m) {
   m.impl("asr_finalize_", &asr_finalize_);
   m.impl("asr_terms_backward_", &asr_terms_backward_);
   m.impl("asr_step_backward_", &asr_step_backward_);
+  m.impl("asr_log_row_", &asr_log_row_);
 }

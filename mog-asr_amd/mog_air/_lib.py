@@ -100,6 +100,7 @@ _SIGS = {
     "mog_eval_detection_means": [P, I, P, P],
     "mog_gather_rows": [P, P, P, I, I, I, P, P, P],
     "mog_synth_canvases": [P, P, I, P, I, I, ULL, ULL, I, P, P, P, P, P],
+    "mog_asr_log_row": [P, I, P, P, P, P] + [P] * 10 + [I, I, P, P],
 }
 
 # entry points that do not return an int status

@@ -680,6 +680,19 @@ class AIRModel(ModelBase):
                 "num_margin": float(ws.margin[0]), "num_min_KL": m(ws.element),
                 "TotLoss": self.loss, "elbo": m(ws.klsum + ws.bce), "accu": self.accuracy}
 
+    log_names = ops.ASR_LOG_NAMES  # the keys of ``log_variables``, in its order
+
+    def log_row_(self, out: torch.Tensor) -> None:
+        """``log_variables`` of the last step (or infer) into the device fp32
+        vector ``out`` [16] on the current stream: one launch
+        (ops.asr_log_row), no host read.  The sums run in float64 on the
+        device, so an entry may differ from the property's fp32 reduction by
+        that reduction's rounding; TotLoss, accu and num_margin are its bits."""
+        ws = self._log_row_out(out)
+        ops.asr_log_row(ws.arec, ws.vkl, ws.zmask, ws.live, ws.bce, ws.mse, ws.area, ws.outl,
+                        ws.size, ws.over, ws.element, ws.klsum, ws.margin, ws.means, out,
+                        slots=[Q[n] for n in ("zkl", "skl", "shkl", "prn")])
+
     # ------------------------------------------------------ generation -----
     _GEN_NOISE = (("eps_shift", True), ("eps_scale", True), ("eps_z", True), ("eps_x", True),
                   ("u_x", False), ("u", False))

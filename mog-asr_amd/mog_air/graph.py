@@ -4,6 +4,7 @@ to the eager step (tests/test_gpu_graph.py).  The reference's batch of 64
 (training_air_original.py:22) is launch-bound without it."""
 from __future__ import annotations
 
+import gc
 from typing import Optional
 
 import torch
@@ -111,6 +112,13 @@ class GraphCapture:
         # every step): force it to be recorded
         self._wcache.invalidate()
         torch.cuda.synchronize(self.device)
+        # A model holds reference cycles (its weight cache's builders), so a
+        # dropped one -- and its captured graph -- waits for the cyclic
+        # collector, which may run at any allocation: destroying a graph while
+        # this capture is open is an error the runtime raises from the
+        # destructor (the process aborts).  Collect before the capture begins
+        # (torch.cuda.graph itself no longer does).
+        gc.collect()
         g = torch.cuda.CUDAGraph()
         self._global_batch = global_batch
         with torch.cuda.graph(g):

@@ -586,6 +586,28 @@ class ModelBase(GlimpseVAE, WeightGradients, GraphCapture, Results):
         m = self._ws.means.detach().cpu().numpy()
         return float(m[0]), float(m[1]), float(m[2]), self.params.global_step
 
+    # the trainers' log row: what ``step`` returns beside the global step
+    log_names = ("loss", "accuracy", "mse")
+
+    def _log_row_out(self, out) -> _Workspace:
+        """The workspace of the last step / infer, once ``out`` is a device
+        fp32 vector of len(log_names) (ValueError otherwise, nothing written)."""
+        ws = self._ws
+        if ws is None:
+            raise RuntimeError("log_row_ before any step or infer")
+        ops._chk(out, "out")
+        if tuple(out.shape) != (len(self.log_names),) or out.device != ws.means.device:
+            raise ValueError(f"out must be [{len(self.log_names)}] on {ws.means.device}, got "
+                             f"{tuple(out.shape)} on {out.device}")
+        return ws
+
+    def log_row_(self, out: torch.Tensor) -> None:
+        """The last step's (or infer's) ``log_names`` values into the device
+        fp32 vector ``out`` on the current stream: one launch, no host read
+        (the bits of the workspace's means; trainer.LogRing)."""
+        ws = self._log_row_out(out)
+        _ops.copy32_batch_([out], [ws.means[:len(self.log_names)]])
+
     def compute_gradients(self, images, targets=None, noise=None, canvas_cotangent=None,
                           global_batch: Optional[int] = None):
         """Forward + backward (+ the data-parallel all-reduce when attached),

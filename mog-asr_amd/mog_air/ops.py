@@ -442,6 +442,57 @@ def eval_detection_means(per_image: torch.Tensor, means: torch.Tensor) -> None:
     _ops.eval_detection_means_(per_image, per_image.shape[0], means)
 
 
+ASR_NQ = 30        # record slots of asr_cell.hip (= asr_model.NQ)
+ASR_LOG_T_MAX = 8  # loop steps the log-row kernel holds
+# the AIR-ASR model's log variables, in the order of its ``log_variables``
+ASR_LOG_NAMES = ("z_pres_kl", "scale_kl", "shift_kl", "vae_kl", "pr_num", "recon", "mse",
+                 "area_loss", "out_loss", "size_loss", "over_loss", "num_margin", "num_min_KL",
+                 "TotLoss", "elbo", "accu")
+
+
+def asr_log_row(arec: torch.Tensor, vkl: torch.Tensor, zmask: torch.Tensor, live: torch.Tensor,
+                bce: torch.Tensor, mse: torch.Tensor, area: torch.Tensor, outl: torch.Tensor,
+                size: torch.Tensor, over: torch.Tensor, element: torch.Tensor,
+                klsum: torch.Tensor, margin: torch.Tensor, means: torch.Tensor,
+                out: torch.Tensor, slots: Sequence[int]) -> None:
+    """out [16] = the AIR-ASR log row (ASR_LOG_NAMES) of the step whose
+    workspace arrays are given, in one launch without a host read
+    (mog_asr_log_row): arec [T, 30, B], vkl / zmask [T, B], live int32 [T] or
+    [T + 1], bce .. klsum [B], margin [1], means [4]; ``slots``: the record
+    slots (zkl, skl, shkl, prn) of arec.  Sums over the executed steps (the sum
+    of live[:T]) and the batch in float64, in a fixed order.  1 <= T <= 8."""
+    _chk(out, "out")
+    if tuple(out.shape) != (len(ASR_LOG_NAMES),):
+        raise ValueError(f"out must be [{len(ASR_LOG_NAMES)}], got {tuple(out.shape)}")
+    _chk(arec, "arec")
+    if arec.dim() != 3 or arec.shape[1] != ASR_NQ or arec.shape[2] < 1:
+        raise ValueError(f"arec must be [T, {ASR_NQ}, B >= 1], got {tuple(arec.shape)}")
+    T, B = arec.shape[0], arec.shape[2]
+    if not 1 <= T <= ASR_LOG_T_MAX:
+        raise ValueError(f"{T} loop steps: the kernel holds 1..{ASR_LOG_T_MAX}")
+    _chk(live, "live", torch.int32)
+    if live.dim() != 1 or live.shape[0] not in (T, T + 1):
+        raise ValueError(f"live must be [{T}] or [{T + 1}], got {tuple(live.shape)}")
+    for t, name, shape in ((vkl, "vkl", (T, B)), (zmask, "zmask", (T, B)), (bce, "bce", (B,)),
+                           (mse, "mse", (B,)), (area, "area", (B,)), (outl, "outl", (B,)),
+                           (size, "size", (B,)), (over, "over", (B,)),
+                           (element, "element", (B,)), (klsum, "klsum", (B,)),
+                           (margin, "margin", (1,)), (means, "means", (4,))):
+        _chk(t, name)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {list(shape)}, got {tuple(t.shape)}")
+    for t, name in ((arec, "arec"), (vkl, "vkl"), (zmask, "zmask"), (live, "live"), (bce, "bce"),
+                    (mse, "mse"), (area, "area"), (outl, "outl"), (size, "size"), (over, "over"),
+                    (element, "element"), (klsum, "klsum"), (margin, "margin"), (means, "means")):
+        if t.device != out.device:
+            raise ValueError(f"{name} is on {t.device}, out on {out.device}")
+    slots = [int(s) for s in slots]
+    if len(slots) != 4 or not all(0 <= s < ASR_NQ for s in slots):
+        raise ValueError(f"slots must be 4 record slots in [0, {ASR_NQ}), got {slots}")
+    _ops.asr_log_row_(B, T, slots, arec, vkl, zmask, live, bce, mse, area, outl, size, over,
+                      element, klsum, margin, means, out)
+
+
 def gather_rows(src: torch.Tensor, idx, out: torch.Tensor, ksrc: Optional[torch.Tensor] = None,
                 kout: Optional[torch.Tensor] = None) -> None:
     """out[b] = src[idx[b]] for the B picks of `idx` (and kout[b] =

@@ -46,7 +46,8 @@ def add_common_args(parser, reader_threads: int):
     train_air_pr.py:40-61) plus this framework's options (not in the
     reference): --iterations, --precision, --test-batch, --synth-per-count,
     --write-synthetic, --device, --resident, --save-every, --restore,
-    --restore-mode, --eval-only, --batch-size, --stream, --stream-seed."""
+    --restore-mode, --eval-only, --batch-size, --stream, --stream-seed,
+    --graph."""
     parser.add_argument("-r", "--results-folder", default="Not Valid")
     parser.add_argument("-k", "-key", "--key", default="")
     parser.add_argument("-gpu", "--gpu", default="-1")
@@ -89,6 +90,10 @@ def add_common_args(parser, reader_threads: int):
                         help="1: every batch is fresh stand-in canvases made on the device "
                              "(records.StreamFeed); needs --iterations and absent dataset files")
     parser.add_argument("--stream-seed", type=int, default=12345)
+    parser.add_argument("--graph", type=int, choices=[0, 1], default=0,
+                        help="1: every iteration is the captured train step "
+                             "(train_step_graphed) and its log row stays on the device until a "
+                             "log line or a state save needs it (LogRing); one device only")
 
 
 def select_gpu(gpu: str) -> None:
@@ -194,6 +199,21 @@ def check_feed_args(args, train_file: str, test_file: str) -> None:
         raise ValueError("--stream 1 needs --iterations: the stream never ends")
     if not 0 <= args.stream_seed < 2 ** 63:
         raise ValueError("--stream-seed must be in [0, 2^63)")
+
+
+def check_graph_args(args, ctx: Dist, annealed=()) -> None:
+    """--graph 1: refused before anything is written where the captured step
+    would refuse the model the entry point builds (graph.GraphCapture._graph_ok):
+    more than one rank, or an annealed hyper-parameter (``annealed``: the
+    names in the model's annealing_schedules) that a capture would freeze."""
+    if not getattr(args, "graph", 0):
+        return
+    if ctx.world > 1:
+        raise ValueError("--graph 1 is the single-device train step, but this run has %d ranks"
+                         % ctx.world)
+    frozen = [n for n in annealed if n != "z_pres_prior_log_odds"]
+    if frozen:
+        raise ValueError("--graph 1: annealed %s would be frozen at capture" % frozen)
 
 
 def results_folder(args, entry: str, name: str, main: bool = True) -> str:
@@ -335,6 +355,36 @@ class LoopState:
     @classmethod
     def from_dict(cls, d: dict) -> "LoopState":
         return cls(**{f.name: d[f.name] for f in dataclasses.fields(cls)})
+
+
+class LogRing:
+    """--graph 1: the log rows of the iterations since the last log line, on
+    the device ([LOG_EACH_ITERATION, len(model.log_names)] fp32).  ``push``
+    has the model write its last step's row into the next free one
+    (``log_row_``: one launch, no host read; the row index is the host's);
+    ``drain`` is the loop's only host read of step results."""
+
+    def __init__(self, model, rows: int = LOG_EACH_ITERATION):
+        import torch
+        self.buf = torch.zeros((rows, len(model.log_names)), device=model.device,
+                               dtype=torch.float32)
+        self.n = 0
+
+    def push(self, model) -> None:
+        if self.n >= self.buf.shape[0]:
+            raise RuntimeError("LogRing is full (%d rows): drain() it before the next push"
+                               % self.buf.shape[0])
+        model.log_row_(self.buf[self.n])
+        self.n += 1
+
+    def drain(self) -> list:
+        """The pushed rows in push order as lists of Python floats (one
+        device-to-host copy; none when nothing was pushed); empties the ring."""
+        if self.n == 0:
+            return []
+        rows = self.buf[:self.n].cpu().tolist()
+        self.n = 0
+        return rows
 
 
 class StateSaver:
@@ -513,6 +563,13 @@ def train_loop(args, train_model, test_model, tr_x, tr_k, test, canvas, log, mod
     states = StateSaver(models_folder, train_model, test_model, feed, ctx)
     save_every = getattr(args, "save_every", SAVE_PARAMS_EACH_ITERATIONS)
     st = restore(args, train_model, test_model, feed, ctx, log)
+    # --graph 1: the captured step; its [loss, accuracy, mse] rows wait in the
+    # ring until a log line, a state save or the end of the loop reads st.rows
+    ring = LogRing(train_model) if getattr(args, "graph", 0) else None
+
+    def drain():
+        if ring is not None:
+            st.rows.extend(ring.drain())
 
     def test_and_log(tag):
         if not ctx.main:
@@ -554,13 +611,20 @@ def train_loop(args, train_model, test_model, tr_x, tr_k, test, canvas, log, mod
             if save_every > 0 and st.step % save_every == 0:
                 if ctx.main:
                     saver.save(train_model.params, st.step)
+                drain()
                 states.save(st)
             x, k, nglobal = feed.next_batch()
-            loss, acc, mse, st.step = train_model.step(x, k, global_batch=nglobal)
+            if ring is not None:
+                train_model.train_step_graphed(x, k, global_batch=nglobal)
+                ring.push(train_model)
+                st.step = train_model.global_step
+            else:
+                loss, acc, mse, st.step = train_model.step(x, k, global_batch=nglobal)
+                st.rows.append([loss, acc, mse])
             if extra_log is not None:
                 extra_log(train_model, st.step)
-            st.rows.append([loss, acc, mse])
             if st.step % LOG_EACH_ITERATION == 0:
+                drain()
                 # (the rows since the last log line: the last LOG_EACH_ITERATION)
                 l0, l1, l2 = ctx.mean(np.mean(st.rows, axis=0), args.device, weight=len(k))
                 st.rows = []
@@ -580,9 +644,11 @@ def train_loop(args, train_model, test_model, tr_x, tr_k, test, canvas, log, mod
                 raise StopIteration
         raise StopIteration
     except StopIteration:
+        drain()  # the loop's end: the rows since the last log line
         if not getattr(args, "eval_only", 0):
             # before the final test, so that an evaluation of this file draws
             # the noise the run's own final test drew
+            drain()  # (every save drains first; here the ring is empty already)
             states.save(st)
         test_and_log("final")
         # the final reconstruction / misclassified grids are tagged 'final',
@@ -613,6 +679,15 @@ def train_loop_asr(args, train_model, test_model, tr_x, tr_k, test, canvas, log,
     states = StateSaver(models_folder, train_model, test_model, feed, ctx)
     save_every = getattr(args, "save_every", SAVE_PARAMS_EACH_ITERATIONS)
     st = restore(args, train_model, test_model, feed, ctx, log)
+    # --graph 1: the captured step; its log rows wait in the ring until a log
+    # line, a state save or the end of the loop reads st.logged
+    ring = LogRing(train_model) if getattr(args, "graph", 0) else None
+
+    def drain():
+        if ring is not None:
+            for row in ring.drain():
+                for n, v in zip(train_model.log_names, row):
+                    st.logged.setdefault(n, []).append(v)
 
     def test_and_log(tag):
         if not ctx.main:
@@ -654,13 +729,21 @@ def train_loop_asr(args, train_model, test_model, tr_x, tr_k, test, canvas, log,
             if save_every > 0 and st.step % save_every == 0:
                 if ctx.main:
                     saver.save(train_model.params, st.step)
+                drain()
                 states.save(st)
             x, k, nglobal = feed.next_batch()
-            _, _, _, st.step = train_model.step(x, k, global_batch=nglobal)
-            lv = train_model.log_variables
-            for n, v in lv.items():
-                st.logged.setdefault(n, []).append(v)
+            if ring is not None:
+                train_model.train_step_graphed(x, k, global_batch=nglobal)
+                ring.push(train_model)
+                st.step = train_model.global_step
+                lv = train_model.log_names  # (the names alone: the values wait in the ring)
+            else:
+                _, _, _, st.step = train_model.step(x, k, global_batch=nglobal)
+                lv = train_model.log_variables
+                for n, v in lv.items():
+                    st.logged.setdefault(n, []).append(v)
             if st.step % LOG_EACH_ITERATION == 0:
+                drain()
                 line = "step:{:6d}\t".format(st.step)
                 # the global batch's means (shard-size weighted over ranks), in
                 # the model's order (a restored ``logged`` may list them in another)
@@ -680,7 +763,9 @@ def train_loop_asr(args, train_model, test_model, tr_x, tr_k, test, canvas, log,
                 raise StopIteration
         raise StopIteration
     except StopIteration:
+        drain()  # the loop's end: the rows since the last log line
         if not getattr(args, "eval_only", 0):
+            drain()  # (every save drains first; here the ring is empty already)
             states.save(st)  # before the final test (see train_loop)
         # the reference logs the step here too (train_air_pr.py:426-430)
         test_and_log(st.step)

@@ -57,6 +57,7 @@ def main(argv=None):
     print(size_min, size_max)
     trainer.check_feed_args(args, train_file, test_file)
     ctx = trainer.distributed_setup(args)  # one process per GPU under torch.distributed.run
+    trainer.check_graph_args(args, ctx)  # (this model anneals nothing)
     folder = trainer.results_folder(args, "train_air_pr.py", name, main=ctx.main)
     log = trainer.build_logger(folder, args, main=ctx.main)
     if ctx.main:

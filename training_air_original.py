@@ -43,6 +43,7 @@ def main(argv=None):
     train_file, test_file, canvas, name, digits = trainer.dataset_files(args, "training_air_original.py")
     trainer.check_feed_args(args, train_file, test_file)
     ctx = trainer.distributed_setup(args)  # one process per GPU under torch.distributed.run
+    trainer.check_graph_args(args, ctx, annealed=("z_pres_prior_log_odds",))
     folder = trainer.results_folder(args, "training_air_original.py", name, main=ctx.main)
     log = trainer.build_logger(folder, args, main=ctx.main)
     if ctx.main:
