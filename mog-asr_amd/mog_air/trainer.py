@@ -1,9 +1,13 @@
 """Training driver behind the kept entry points (training_air_original.py,
-train_air_pr.py): results-folder handling, logging, the input pipeline, the
-train / test model pair sharing one variable scope, the iteration loop with
-the reference's logging / testing / checkpoint cadence, and the end-of-data
-(OutOfRangeError) epilogue — training_air_original.py:18-503 and
-train_air_pr.py:18-400 restated around ``AIRModel.step`` / ``infer``.
+train_air_pr.py): results-folder handling, logging and the input pipeline
+(``setup_run``, the head of both main()s), the train / test model pair sharing
+one variable scope (``model_pair``), and the one iteration loop with the
+reference's logging / testing / checkpoint cadence and its end-of-data
+(OutOfRangeError) epilogue (``train_loop``) — training_air_original.py:18-503
+and train_air_pr.py:18-400 restated around ``AIRModel.step`` / ``infer``.
+What the two trainers do differently inside the loop -- how a step's numbers
+are kept, the log line, what a test pass reports -- is AIR_STYLE / ASR_STYLE,
+which the entry points pass by name.
 
 Image grids (training_air_original.py:368-411, :445-490): every
 IMAGE_SAVE_ITERATION iterations and at the end, the test model's
@@ -168,6 +172,21 @@ def attach_data_parallel(train_model, ctx: Dist) -> None:
         attach(train_model)
 
 
+def model_pair(make, ctx: Dist, **config):
+    """The train model and the test model sharing its variable scope
+    (training_air_original.py:158-211): ``make(None, None, **config)`` twice,
+    with independent Monte-Carlo noise per rank; the train model is attached
+    to the data-parallel group."""
+    models = []
+    for i in range(2):
+        print("Creating {0} model...".format("training" if i == 0 else "testing"))
+        models.append(make(None, None, train=(i == 0), reuse=(i == 1),
+                           noise_seed=1235 + ctx.rank, grad_world=ctx.world if i == 0 else 1,
+                           **config))
+    attach_data_parallel(models[0], ctx)
+    return models
+
+
 def dataset_files(args, entry: str):
     """(train file, test file, canvas size, common name), as the entry points
     derive them from -data/-dn/-dl/-ds (training_air_original.py:67-91)."""
@@ -314,6 +333,31 @@ def load_data(args, train_file, test_file, digits, log):
     return tr_x, tr_k, test
 
 
+def setup_run(args, entry: str, annealed=()):
+    """The head of both entry points' main() (training_air_original.py:67-135):
+    the argument refusals before anything is written, the results folder
+    before the logger, the data before the models.  ``entry``: the entry
+    point's file name; ``annealed``: see check_graph_args.  Returns (ctx,
+    results folder, logger, train images, train counts, test tuple, canvas
+    size, digits)."""
+    train_file, test_file, canvas, name, digits = dataset_files(args, entry)
+    check_feed_args(args, train_file, test_file)
+    ctx = distributed_setup(args)  # one process per GPU under torch.distributed.run
+    check_graph_args(args, ctx, annealed=annealed)
+    folder = results_folder(args, entry, name, main=ctx.main)
+    log = build_logger(folder, args, main=ctx.main)
+    if ctx.main:
+        package = os.path.dirname(os.path.abspath(__file__))
+        copy_sources(folder, [os.path.dirname(os.path.dirname(package)), package])
+    log.info("Creating input pipeline...")
+    if not ctx.main:
+        ctx.barrier()  # rank 0 writes synthetic data first when asked to
+    tr_x, tr_k, test = load_data(args, train_file, test_file, digits, log)
+    if ctx.main:
+        ctx.barrier()
+    return ctx, folder, log, tr_x, tr_k, test, canvas, digits
+
+
 class Saver:
     """tf.train.Saver(max_to_keep=3) stand-in: <folder>/<prefix>-<step>.npz
     holding every variable under its TF name."""
@@ -335,7 +379,7 @@ class Saver:
 
 @dataclasses.dataclass
 class LoopState:
-    """What the iteration loops carry from one iteration to the next beside
+    """What the iteration loop carries from one iteration to the next beside
     the models and the feed (saved with the train state, checkpoint.py).
     ``rows`` (AIR): the [loss, accuracy, mse] of every iteration since the
     last log line; ``logged`` (AIR-ASR): the log variables since then."""
@@ -547,129 +591,97 @@ def run_test(test_model, test, canvas: int, batch: int, evaluator=None):
     return loss, acc, mse, np.concatenate(scales), np.concatenate(shifts), np.concatenate(nums)
 
 
-def train_loop(args, train_model, test_model, tr_x, tr_k, test, canvas, log, models_folder,
-               extra_log=None, ctx: Optional[Dist] = None):
-    """The iteration loop of training_air_original.py:226-503 (logging every
-    20, testing every 200, parameters and the train state every --save-every
-    (10,000) iterations; the final test when the input runs out).  With
-    --restore the loop starts from the saved state; --eval-only 1 runs the
-    epilogue alone."""
-    ctx = ctx or Dist()
-    resident = resident_ok(args, tr_x, test, test_model, log)
-    feed = make_feed(args, tr_x, tr_k, ctx, resident)
-    test_dev, evaluator = (resident_test_set(args, test, canvas, test_model)
-                           if resident and ctx.main else (None, None))
-    saver = Saver(models_folder, "air-model")
-    states = StateSaver(models_folder, train_model, test_model, feed, ctx)
-    save_every = getattr(args, "save_every", SAVE_PARAMS_EACH_ITERATIONS)
-    st = restore(args, train_model, test_model, feed, ctx, log)
-    # --graph 1: the captured step; its [loss, accuracy, mse] rows wait in the
-    # ring until a log line, a state save or the end of the loop reads st.rows
-    ring = LogRing(train_model) if getattr(args, "graph", 0) else None
+METRICS = "test:{}\tprecision:{}\trecall:{}\tgtIoU:{:.4f}\tdetectionIoU:{:.4f}\t{}:{:.4f}"
+BEST = "{} Best: elbo:{}\taccu:{}\tmse:{}\tiou:{}"
 
-    def drain():
-        if ring is not None:
-            st.rows.extend(ring.drain())
 
-    def test_and_log(tag):
-        if not ctx.main:
-            ctx.barrier()
-            return 0.0, 0.0, 0.0, 0.0
-        if evaluator is not None:
-            tl, ta, tm, _ = run_test(test_model, test_dev, canvas, args.test_batch, evaluator)
-        else:
-            tl, ta, tm, sc, sh, nd = run_test(test_model, test, canvas, args.test_batch)
-        ctx.barrier()
+def _follow_best(log, st: LoopState, results: list) -> None:
+    """After a test pass: its results are the best ones when the train loss has
+    reached a new minimum since the last update."""
+    if st.update_flag:
+        st.update_flag = False
+        st.best = results
+    log.info(BEST.format("Current", *st.best))
+
+
+class AirStyle:
+    """What training_air_original.py:226-503 does its own way in train_loop: a
+    step's [loss, accuracy, mse] is a row of LoopState.rows; the best results
+    follow the periodic tests only, and the final test is tagged 'final'."""
+    grids_per_count = True  # generation grids for every object count of -dn
+
+    def step_row(self, model, fetched):
+        return list(fetched[:3])
+
+    def keep(self, st, model, rows):
+        st.rows.extend(rows)
+
+    def log_line(self, st, model, mean):
+        """(train loss, log line) of the rows since the last log line (the
+        last LOG_EACH_ITERATION), which are dropped."""
+        l0, l1, l2 = mean(np.mean(st.rows, axis=0))
+        st.rows = []
+        return l0, ("iteration {}\ttrain loss {:.3f}\ttrain accuracy {:.2f}, "
+                    "train mse {:.3f}".format(st.step, l0, l1, l2))
+
+    def report(self, log, st, final, sums, detections, test_model):
         log.info("iteration {}\ttest loss {:.3f}\ttest accuracy {:.2f}, test mse {:.3f}".format(
-            tag, tl, ta, tm))
-        if evaluator is not None:
-            p, r, gt_iou, det_iou, g_iou = evaluator.result()
-        else:
-            p, r, gt_iou, det_iou, g_iou = evaluation(test[3], test[4], sh, sc, nd, csize=canvas)
+            "final" if final else st.step, *sums))
+        d = detections()
         # integer steps are padded to 6 as training_air_original.py:357 does
-        # ('final' is printed as is)
-        step_tag = "{:6d}".format(tag) if isinstance(tag, int) else tag
-        log.info("test:{}\tprecision:{}\trecall:{}\tgtIoU:{:.4f}\tdetectionIoU:{:.4f}"
-                 "\tglobaliou:{:.4f}".format(step_tag, p, r, gt_iou, det_iou, g_iou))
-        return tl, ta, tm, g_iou
-
-    summary_folder = os.path.join(os.path.dirname(os.path.normpath(models_folder)), "summary")
-    digits = [int(c) for c in getattr(args, "dig_num", "")]
-    vis_n = args.test_batch if getattr(args, "test_batch", 0) > 0 else len(test[1])
-
-    def save_images(tag, generations=True, gen_tag=None):
-        if not ctx.main or getattr(args, "no_images", False):
-            return
-        from .visualize import save_visualizations
-        save_visualizations(test_model, test[0][:vis_n], test[1][:vis_n], summary_folder, tag,
-                            digits=digits, num=NUM_IMAGES_TO_SAVE, generations=generations,
-                            gen_tag=gen_tag)
-
-    log.info("Training...\n")
-    try:
-        while not getattr(args, "eval_only", 0):
-            if save_every > 0 and st.step % save_every == 0:
-                if ctx.main:
-                    saver.save(train_model.params, st.step)
-                drain()
-                states.save(st)
-            x, k, nglobal = feed.next_batch()
-            if ring is not None:
-                train_model.train_step_graphed(x, k, global_batch=nglobal)
-                ring.push(train_model)
-                st.step = train_model.global_step
-            else:
-                loss, acc, mse, st.step = train_model.step(x, k, global_batch=nglobal)
-                st.rows.append([loss, acc, mse])
-            if extra_log is not None:
-                extra_log(train_model, st.step)
-            if st.step % LOG_EACH_ITERATION == 0:
-                drain()
-                # (the rows since the last log line: the last LOG_EACH_ITERATION)
-                l0, l1, l2 = ctx.mean(np.mean(st.rows, axis=0), args.device, weight=len(k))
-                st.rows = []
-                log.info("iteration {}\ttrain loss {:.3f}\ttrain accuracy {:.2f}, "
-                         "train mse {:.3f}".format(st.step, l0, l1, l2))
-                if l0 < st.min_loss:
-                    st.update_flag, st.min_loss = True, l0
-            if st.step % TEST_EACH_ITERATION == 0:
-                tl, ta, tm, g_iou = test_and_log(st.step)
-                if st.update_flag:
-                    st.update_flag = False
-                    st.best = [tl, ta, tm, g_iou]
-                log.info("Current Best: elbo:{}\taccu:{}\tmse:{}\tiou:{}".format(*st.best))
-            if st.step % IMAGE_SAVE_ITERATION == 0:
-                save_images(st.step)
-            if args.iterations and st.step >= args.iterations:
-                raise StopIteration
-        raise StopIteration
-    except StopIteration:
-        drain()  # the loop's end: the rows since the last log line
-        if not getattr(args, "eval_only", 0):
-            # before the final test, so that an evaluation of this file draws
-            # the noise the run's own final test drew
-            drain()  # (every save drains first; here the ring is empty already)
-            states.save(st)
-        test_and_log("final")
-        # the final reconstruction / misclassified grids are tagged 'final',
-        # the final generation grids with the step (training_air_original.py:478-483)
-        save_images("final", gen_tag=st.step)
-        log.info("Final Best: elbo:{}\taccu:{}\tmse:{}\tiou:{}".format(*st.best))
-        log.info("\ntraining has ended\n")
-    return st.step
+        log.info(METRICS.format("final" if final else "{:6d}".format(st.step), *d[:4],
+                                "globaliou", d[4]))
+        if not final:
+            _follow_best(log, st, [*sums, d[4]])
 
 
-TESET_EACH_ITERATION = 200  # (sic) train_air_pr.py:31
+class AsrStyle:
+    """What train_air_pr.py:284-400 does its own way in train_loop: a step's
+    log variables are kept per name in LoopState.logged; every test, the final
+    one included, is tagged with the step (train_air_pr.py:426-430), logs the
+    test model's log variables and is followed by the best results."""
+    grids_per_count = False  # train_air_pr.py:362-398: the model's loop draws the counts
+
+    def step_row(self, model, fetched):
+        return list(model.log_variables.values())
+
+    def keep(self, st, model, rows):
+        for row in rows:
+            for n, v in zip(model.log_names, row):
+                st.logged.setdefault(n, []).append(v)
+
+    def log_line(self, st, model, mean):
+        """(TotLoss, log line) of the variables since the last log line, which
+        are dropped: the means in the model's order (a restored ``logged`` may
+        list them in another)."""
+        names = model.log_names
+        means = mean([np.mean(st.logged[n]) for n in names])
+        st.logged = {}
+        return float(means[names.index("TotLoss")]), "step:{:6d}\t".format(st.step) + "".join(
+            "{}:{:.4f}\t".format(n, v) for n, v in zip(names, means))
+
+    def report(self, log, st, final, sums, detections, test_model):
+        d = detections()
+        log.info(METRICS.format("{:6d}".format(st.step), *d[:4], "global_iou", d[4]))
+        lv = test_model.log_variables  # (as the test set's last chunk left them)
+        log.info("test:{:6d}\t".format(st.step) +
+                 "".join("{}:{:.4f}\t".format(n, v) for n, v in lv.items()))
+        _follow_best(log, st, [lv["elbo"], lv["accu"], lv["mse"], d[4]])
 
 
-def train_loop_asr(args, train_model, test_model, tr_x, tr_k, test, canvas, log, models_folder,
-                   ctx: Optional[Dist] = None):
-    """The iteration loop of train_air_pr.py:284-400: every step fetches the
-    model's log variables; every 20 iterations their means are logged, every
-    200 the test model runs on the test set (log variables + detection
-    metrics); parameters and the train state are saved every --save-every
-    (10,000) iterations; the final test when the input runs out.  Data
-    parallel, --restore and --eval-only as train_loop."""
+AIR_STYLE, ASR_STYLE = AirStyle(), AsrStyle()
+
+
+def train_loop(args, train_model, test_model, tr_x, tr_k, test, canvas, log, models_folder,
+               ctx: Optional[Dist] = None, *, style):
+    """The iteration loop of both trainers (training_air_original.py:226-503,
+    train_air_pr.py:284-400): logging every 20 iterations, testing every 200,
+    image grids every 500, parameters and the train state every --save-every
+    (10,000); the final test when the input runs out or --iterations is
+    reached.  ``style`` (AIR_STYLE / ASR_STYLE) is what the two differ in: how
+    a step's numbers are kept, the log line and what a test pass reports.
+    With --restore the loop starts from the saved state; --eval-only 1 runs
+    the epilogue alone."""
     ctx = ctx or Dist()
     resident = resident_ok(args, tr_x, test, test_model, log)
     feed = make_feed(args, tr_x, tr_k, ctx, resident)
@@ -677,100 +689,88 @@ def train_loop_asr(args, train_model, test_model, tr_x, tr_k, test, canvas, log,
                            if resident and ctx.main else (None, None))
     saver = Saver(models_folder, "air-model")
     states = StateSaver(models_folder, train_model, test_model, feed, ctx)
-    save_every = getattr(args, "save_every", SAVE_PARAMS_EACH_ITERATIONS)
     st = restore(args, train_model, test_model, feed, ctx, log)
     # --graph 1: the captured step; its log rows wait in the ring until a log
-    # line, a state save or the end of the loop reads st.logged
-    ring = LogRing(train_model) if getattr(args, "graph", 0) else None
+    # line, a state save or the end of the loop reads st.rows / st.logged
+    ring = LogRing(train_model) if args.graph else None
 
     def drain():
         if ring is not None:
-            for row in ring.drain():
-                for n, v in zip(train_model.log_names, row):
-                    st.logged.setdefault(n, []).append(v)
+            style.keep(st, train_model, ring.drain())
 
-    def test_and_log(tag):
+    def save_state():
+        drain()
+        states.save(st)
+
+    def test_pass(final=False):
         if not ctx.main:
             ctx.barrier()
             return
         if evaluator is not None:
-            run_test(test_model, test_dev, canvas, args.test_batch, evaluator)
-            ctx.barrier()
-            p, r, gt_iou, det_iou, g_iou = evaluator.result()
+            tl, ta, tm, _ = run_test(test_model, test_dev, canvas, args.test_batch, evaluator)
+            detections = evaluator.result
         else:
             tl, ta, tm, sc, sh, nd = run_test(test_model, test, canvas, args.test_batch)
-            ctx.barrier()
-            p, r, gt_iou, det_iou, g_iou = evaluation(test[3], test[4], sh, sc, nd, csize=canvas)
-        log.info("test:{:6d}\tprecision:{}\trecall:{}\tgtIoU:{:.4f}\tdetectionIoU:{:.4f}"
-                 "\tglobal_iou:{:.4f}".format(tag, p, r, gt_iou, det_iou, g_iou))
-        lv = test_model.log_variables
-        if st.update_flag:
-            st.update_flag = False
-            st.best = [lv["elbo"], lv["accu"], lv["mse"], g_iou]
-        log.info("test:{:6d}\t".format(tag) +
-                 "".join("{}:{:.4f}\t".format(n, v) for n, v in lv.items()))
-        log.info("Current Best: elbo:{}\taccu:{}\tmse:{}\tiou:{}".format(*st.best))
+
+            def detections():
+                return evaluation(test[3], test[4], sh, sc, nd, csize=canvas)
+        ctx.barrier()
+        style.report(log, st, final, (tl, ta, tm), detections, test_model)
 
     summary_folder = os.path.join(os.path.dirname(os.path.normpath(models_folder)), "summary")
-    vis_n = args.test_batch if getattr(args, "test_batch", 0) > 0 else len(test[1])
+    vis_n = args.test_batch if args.test_batch > 0 else len(test[1])
+    digits = [int(c) for c in args.dig_num] if style.grids_per_count else None
 
     def save_images(tag, gen_tag=None):
-        # train_air_pr.py:362-398: the reconstruction grids and one pair of
-        # generation grids (the model's loop draws the counts)
-        if not ctx.main or getattr(args, "no_images", False):
+        if not ctx.main or args.no_images:
             return
         from .visualize import save_visualizations
         save_visualizations(test_model, test[0][:vis_n], test[1][:vis_n], summary_folder, tag,
-                            digits=None, num=NUM_IMAGES_TO_SAVE, gen_tag=gen_tag)
+                            digits=digits, num=NUM_IMAGES_TO_SAVE, gen_tag=gen_tag)
 
     log.info("Training...\n")
-    try:
-        while not getattr(args, "eval_only", 0):
-            if save_every > 0 and st.step % save_every == 0:
-                if ctx.main:
-                    saver.save(train_model.params, st.step)
-                drain()
-                states.save(st)
+    while not args.eval_only:
+        if args.save_every > 0 and st.step % args.save_every == 0:
+            if ctx.main:
+                saver.save(train_model.params, st.step)
+            save_state()
+        try:
             x, k, nglobal = feed.next_batch()
-            if ring is not None:
-                train_model.train_step_graphed(x, k, global_batch=nglobal)
-                ring.push(train_model)
-                st.step = train_model.global_step
-                lv = train_model.log_names  # (the names alone: the values wait in the ring)
-            else:
-                _, _, _, st.step = train_model.step(x, k, global_batch=nglobal)
-                lv = train_model.log_variables
-                for n, v in lv.items():
-                    st.logged.setdefault(n, []).append(v)
-            if st.step % LOG_EACH_ITERATION == 0:
-                drain()
-                line = "step:{:6d}\t".format(st.step)
-                # the global batch's means (shard-size weighted over ranks), in
-                # the model's order (a restored ``logged`` may list them in another)
-                means = ctx.mean([np.mean(st.logged[n]) for n in lv], args.device,
-                                 weight=len(k))
-                for n, v in zip(lv, means):
-                    if n == "TotLoss" and v < st.min_loss:
-                        st.min_loss, st.update_flag = float(v), True
-                    line += "{}:{:.4f}\t".format(n, v)
-                log.info(line)
-                st.logged = {}
-            if st.step % TESET_EACH_ITERATION == 0:
-                test_and_log(st.step)
-            if st.step % IMAGE_SAVE_ITERATION == 0:
-                save_images(st.step)
-            if args.iterations and st.step >= args.iterations:
-                raise StopIteration
-        raise StopIteration
-    except StopIteration:
-        drain()  # the loop's end: the rows since the last log line
-        if not getattr(args, "eval_only", 0):
-            drain()  # (every save drains first; here the ring is empty already)
-            states.save(st)  # before the final test (see train_loop)
-        # the reference logs the step here too (train_air_pr.py:426-430)
-        test_and_log(st.step)
-        # the final generation grids are tagged with the step (train_air_pr.py:462-469)
-        save_images("final", gen_tag=st.step)
-        log.info("Final Best: elbo:{}\taccu:{}\tmse:{}\tiou:{}".format(*st.best))
-        log.info("\ntraining has ended\n")
+        except StopIteration:  # the end of the data (the reference's OutOfRangeError)
+            break
+        if ring is not None:
+            train_model.train_step_graphed(x, k, global_batch=nglobal)
+            ring.push(train_model)
+            st.step = train_model.global_step
+        else:
+            fetched = train_model.step(x, k, global_batch=nglobal)
+            st.step = fetched[3]
+            style.keep(st, train_model, [style.step_row(train_model, fetched)])
+        if st.step % LOG_EACH_ITERATION == 0:
+            drain()
+            # the global batch's means (shard-size weighted over ranks)
+            loss, line = style.log_line(
+                st, train_model, lambda v: ctx.mean(v, args.device, weight=len(k)))
+            log.info(line)
+            if loss < st.min_loss:
+                st.update_flag, st.min_loss = True, loss
+        # (train_air_pr.py:31 spells its constant TESET_EACH_ITERATION; both are 200)
+        if st.step % TEST_EACH_ITERATION == 0:
+            test_pass()
+        if st.step % IMAGE_SAVE_ITERATION == 0:
+            save_images(st.step)
+        if args.iterations and st.step >= args.iterations:
+            break
+    drain()  # the loop's end: the rows since the last log line
+    if not args.eval_only:
+        # before the final test, so that an evaluation of this file draws the
+        # noise the run's own final test drew
+        save_state()
+    test_pass(final=True)
+    # the final reconstruction / misclassified grids are tagged 'final', the
+    # final generation grids with the step (training_air_original.py:478-483,
+    # train_air_pr.py:462-469)
+    save_images("final", gen_tag=st.step)
+    log.info(BEST.format("Final", *st.best))
+    log.info("\ntraining has ended\n")
     return st.step

@@ -1,8 +1,8 @@
 """What the trainers' --graph switch buys, measured on the GPU host (DESIGN.md
 §4.18), fp32, on the offline stand-in data of mog_air.datasets.
 
- (a) Loop cost.  200 iterations of the statements train_loop / train_loop_asr
-     run per iteration -- feed.next_batch(), the step, the log row, and every
+ (a) Loop cost.  200 iterations of the statements trainer.train_loop runs per
+     iteration (in either style) -- feed.next_batch(), the step, the log row, and every
      20 iterations the log line's means -- for the AIR model of
      training_air_original.py (6 loop steps) and the AIR-ASR model of
      train_air_pr.py -gm 100 -gne 10, at batch 64 and 256 (both below
@@ -67,7 +67,7 @@ def clock(fn):
 
 
 def window(kind, graph, m, feed):
-    """ITERS iterations of the loop body (trainer.train_loop / train_loop_asr)."""
+    """ITERS iterations of the loop body (trainer.train_loop, in ``kind``'s style)."""
     from mog_air import trainer
     every = trainer.LOG_EACH_ITERATION
     ring = trainer.LogRing(m) if graph else None

@@ -40,49 +40,27 @@ def main(argv=None):
     np.random.seed(1234)
     from mog_air.air_model import AIRModel
 
-    train_file, test_file, canvas, name, digits = trainer.dataset_files(args, "training_air_original.py")
-    trainer.check_feed_args(args, train_file, test_file)
-    ctx = trainer.distributed_setup(args)  # one process per GPU under torch.distributed.run
-    trainer.check_graph_args(args, ctx, annealed=("z_pres_prior_log_odds",))
-    folder = trainer.results_folder(args, "training_air_original.py", name, main=ctx.main)
-    log = trainer.build_logger(folder, args, main=ctx.main)
-    if ctx.main:
-        trainer.copy_sources(folder, [ROOT, os.path.join(ROOT, "mog-asr_amd", "mog_air")])
-
-    log.info("Creating input pipeline...")
-    if not ctx.main:
-        ctx.barrier()  # rank 0 writes synthetic data first when asked to
-    tr_x, tr_k, test = trainer.load_data(args, train_file, test_file, digits, log)
-    if ctx.main:
-        ctx.barrier()
-
-    models = []
-    for i in range(2):
-        print("Creating {0} model...".format("training" if i == 0 else "testing"))
-        models.append(AIRModel(
-            None, None, max_steps=MAX_STEPS, max_digits=MAX_STEPS, rnn_units=256,
-            canvas_size=canvas, windows_size=28, vae_latent_dimensions=50,
-            vae_recognition_units=(512, 256), vae_generative_units=(256, 512),
-            scale_prior_mean=-1.0, scale_prior_variance=0.05, shift_prior_mean=0.0,
-            shift_prior_variance=1.0, vae_prior_mean=0.0, vae_prior_variance=1.0,
-            vae_likelihood_std=0.3, scale_hidden_units=64, shift_hidden_units=64,
-            z_pres_hidden_units=64, z_pres_prior_log_odds=-0.01, z_pres_temperature=1.0,
-            stopping_threshold=0.99, learning_rate=1e-4, gradient_clipping_norm=1.0,
-            cnn=bool(args.cnn), cnn_filters=args.cnn_filters,
-            num_summary_images=NUM_IMAGES_TO_SAVE,
-            train=(i == 0), reuse=(i == 1), scope="air",
-            annealing_schedules={"z_pres_prior_log_odds": {
-                "init": 10000.0, "min": 0.000000001, "factor": 0.1, "iters": 3000,
-                "staircase": False, "log": True}},
-            num_prior=digits if args.add_prior else None,
-            device=args.device, seed=1235, precision=args.precision,
-            noise_seed=1235 + ctx.rank,  # independent Monte-Carlo noise per rank
-            grad_world=ctx.world if i == 0 else 1))
-    train_model, test_model = models
-    trainer.attach_data_parallel(train_model, ctx)
+    ctx, folder, log, tr_x, tr_k, test, canvas, digits = trainer.setup_run(
+        args, "training_air_original.py", annealed=("z_pres_prior_log_odds",))
+    train_model, test_model = trainer.model_pair(
+        AIRModel, ctx, max_steps=MAX_STEPS, max_digits=MAX_STEPS, rnn_units=256,
+        canvas_size=canvas, windows_size=28, vae_latent_dimensions=50,
+        vae_recognition_units=(512, 256), vae_generative_units=(256, 512),
+        scale_prior_mean=-1.0, scale_prior_variance=0.05, shift_prior_mean=0.0,
+        shift_prior_variance=1.0, vae_prior_mean=0.0, vae_prior_variance=1.0,
+        vae_likelihood_std=0.3, scale_hidden_units=64, shift_hidden_units=64,
+        z_pres_hidden_units=64, z_pres_prior_log_odds=-0.01, z_pres_temperature=1.0,
+        stopping_threshold=0.99, learning_rate=1e-4, gradient_clipping_norm=1.0,
+        cnn=bool(args.cnn), cnn_filters=args.cnn_filters,
+        num_summary_images=NUM_IMAGES_TO_SAVE, scope="air",
+        annealing_schedules={"z_pres_prior_log_odds": {
+            "init": 10000.0, "min": 0.000000001, "factor": 0.1, "iters": 3000,
+            "staircase": False, "log": True}},
+        num_prior=digits if args.add_prior else None,
+        device=args.device, seed=1235, precision=args.precision)
     log.info("Initializing variables...")
     return trainer.train_loop(args, train_model, test_model, tr_x, tr_k, test, canvas, log,
-                              os.path.join(folder, "models"), ctx=ctx)
+                              os.path.join(folder, "models"), ctx=ctx, style=trainer.AIR_STYLE)
 
 
 if __name__ == "__main__":
