@@ -174,7 +174,8 @@ int mog_stn_forward_periodic(const float* U, int u_period, int N, int Hin, int W
  * stored only on the rows part_rows[n] = lo | hi << 16 (even bounds; rows
  * outside are exactly +0 for axis-aligned theta; all rows otherwise; 0 for an
  * inactive image).  mog_recon_loss sums T such part sets in step order
- * (air_model.py:580-588, 665-675), bit-identical to accumulating. */
+ * (air_model.py:580-588, 665-675), bit-identical to accumulating.
+ * Hout < 65536 (the two bounds share one int); MOG_ERR_INVALID otherwise. */
 int mog_stn_write_parts(const float* U, int N, int Hin, int Win, const float* theta, int Hout,
                         int Wout, const float* z, const float* mask, float* parts,
                         int* part_rows, void* stream);
@@ -184,7 +185,14 @@ int mog_stn_write_parts(const float* U, int N, int Hin, int Win, const float* th
  * (may be NULL).  Writes dU [N, Hin*Win] (may be NULL), dtheta [N, 6] (may be
  * NULL) and dot[n] = sum_p G[n,p] * out[n,p] (may be NULL).  u_period /
  * g_period > 0: image n reads U / G row n % period (all loop steps of a batch
- * in one launch against the shared canvas input or canvas gradient). */
+ * in one launch against the shared canvas input or canvas gradient).
+ * Limits (MOG_ERR_INVALID beyond them, nothing launched): the source image is
+ * staged in LDS, one wave and one slice per image, so Hin * Win <= 16384, and
+ * the slice -- Hin*Win floats rounded up to 4, twice that when dU is wanted,
+ * plus 4 Hout -- must fit the CU's 160 KiB (any Hout <= 2048 does at the
+ * largest source).  Slices above 20 KiB lower the images per workgroup from
+ * 4 towards 1; above 64 KiB (Hin * Win > 8192 with dU) the launch still
+ * succeeds on gfx950.  The three entry points below share these limits. */
 int mog_stn_backward(const float* U, int N, int Hin, int Win, const float* theta, int Hout,
                      int Wout, const float* G, const float* gscale, float* dU, float* dtheta,
                      float* dot, int u_period, int g_period, void* stream);

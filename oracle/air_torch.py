@@ -23,10 +23,12 @@ from .air_oracle import AirConfig, f32log, marginal_objective, param_specs
 
 
 def _linspace(n: int, dtype) -> torch.Tensor:
-    # TF LinSpace in fp32: start + step*i, last = stop (transformer.py:119-136)
+    # TF LinSpace in fp32: start + step*i, last = stop (transformer.py:119-136);
+    # one element is the start, -1 (air_ref.c linspace_at, mog_linspace)
+    if n == 1:
+        return torch.full((1,), -1.0, dtype=dtype)
     i = np.arange(n, dtype=np.float32)
-    v = np.float32(-1.0) + np.float32(2.0 / (n - 1)) * i if n > 1 else np.array([-1.0])
-    v = v.astype(np.float32)
+    v = (np.float32(-1.0) + np.float32(2.0 / (n - 1)) * i).astype(np.float32)
     v[-1] = 1.0
     return torch.from_numpy(v).to(dtype)
 
