@@ -16,12 +16,69 @@ from .asr_oracle import P_ROOT, AsrConfig
 
 
 def _sce(z, x):
-    """tf.nn.sigmoid_cross_entropy_with_logits(labels=z, logits=x)."""
-    return torch.clamp(x, min=0.0) - x * z + torch.log1p(torch.exp(-torch.abs(x)))
+    """tf.nn.sigmoid_cross_entropy_with_logits(labels=z, logits=x), in TF's own
+    form (selects on x >= 0, no abs): the same values as max(x, 0) - x z +
+    log1p(exp(-|x|)), and the gradient sigmoid(x) - z at x == 0 too, where
+    clamp' + abs' would give 1 - z."""
+    pos = x >= 0
+    zero = torch.zeros_like(x)
+    return torch.where(pos, x, zero) - x * z + torch.log1p(torch.exp(torch.where(pos, -x, x)))
 
 
 def _logit8(p):
     return torch.log(p + 1e-8) - torch.log(1.0 - p + 1e-8)
+
+
+def structural_terms(cfg: AsrConfig, scale, shift, zprob, prn, zsum_reduce=None,
+                     global_batch=None):
+    """The structural regularisers of air_number_bbox_location.py:964-1069 from
+    the executed steps' records: scale / zprob / prn [B, Tx], shift [B, Tx, 2].
+    Returns area, out, size, overlap, pr, element [B] and the scalar margin.
+
+    The gradients follow TF 1.12 where PyTorch's differ at ties: Maximum gives
+    the gradient to its first operand (torch.maximum halves it), ReduceMin
+    splits it evenly over tied minima (torch's min(dim) picks one index).
+    tf.maximum(x, 0) passes the gradient at x == 0 and so does
+    torch.clamp(x, min=0); Abs' = sign, 0 at 0, in both: those two stay."""
+    dt = scale.dtype
+    B, Tx = scale.shape
+    Cf = float(cfg.canvas_size)
+    sc = scale * Cf
+    amin, amax = cfg.constrains_area_minmax
+    area = torch.clamp(amax - sc, min=0.0) + torch.clamp(sc - amin, min=0.0)
+    area = area.mean(1) if Tx > 0 else area.sum(1)  # (no executed step: 0, not 0 / 0)
+    cx = (shift[..., 0] + 1.0) * Cf / 2.0
+    cy = (shift[..., 1] + 1.0) * Cf / 2.0
+    outl = (torch.clamp(-(cx - 0.5 * sc), min=0) + torch.clamp(-(cy - 0.5 * sc), min=0) +
+            torch.clamp(cx + 0.5 * sc - Cf, min=0) + torch.clamp(cy + 0.5 * sc - Cf, min=0)).sum(1)
+    size = torch.clamp((sc[:, :, None] - sc[:, None, :]).abs() - 3.0, min=0).sum((1, 2))
+    ax = (cx[:, :, None] - cx[:, None, :]).abs()
+    ay = (cy[:, :, None] - cy[:, None, :]).abs()
+    md = torch.where(ax >= ay, ax, ay)
+    smean = (sc[:, :, None] + sc[:, None, :]) / 2.0
+    eye = torch.eye(Tx, dtype=dt)
+    over = (torch.clamp(smean - md, min=0) * (1.0 - eye)).sum((1, 2))
+    pr = (prn.sum(1) + cfg.constrains_area_gamma * area + over * cfg.constrains_bbox_gamma +
+          outl * cfg.constrains_bbox_gamma + size * cfg.constrains_sharesize_gamma)
+    margin = torch.zeros((), dtype=dt)
+    elem = torch.zeros(B, dtype=dt)
+    if cfg.constrains_margin_gamma > 1e-8:
+        cons = list(cfg.constrains_num)
+        obj = torch.tensor([[1.0 if t < k else 0.0 for t in range(Tx)] for k in cons], dtype=dt)
+        mo = obj.mean(0)
+        if zsum_reduce is None:
+            pm = zprob.mean(0)
+        else:  # global value, gradient through this shard's own terms only
+            zl = zprob.sum(0)
+            zg = torch.as_tensor(zsum_reduce(zl.detach().clone()), dtype=dt)
+            pm = (zl + (zg - zl.detach())) / float(global_batch or B)
+        margin = (_sce(mo, _logit8(pm)) * cfg.constrains_margin_gamma).sum()
+        ce = _sce(obj[None], _logit8(zprob)[:, None, :]).sum(2)
+        tied = (ce == ce.min(1, keepdim=True).values).to(dt)
+        w = (tied / tied.sum(1, keepdim=True)).detach()
+        elem = (ce * w).sum(1) * cfg.constrains_num_element_gamma
+    return {"area": area, "out": outl, "size": size, "overlap": over, "pr": pr,
+            "margin": margin, "element": elem}
 
 
 def asr_forward(cfg: AsrConfig, P, noise, images, targets=None, canvas_cotangent=None,
@@ -149,37 +206,10 @@ def asr_forward(cfg: AsrConfig, P, noise, images, targets=None, canvas_cotangent
         rc = torch.clamp(canvas, 0.0, 1.0)
         bce = -(images * torch.log(rc + 1e-10) + (1.0 - images) * torch.log(1.0 - rc + 1e-10)).sum(1)
         elbo = elbo + bce
-    Cf = float(C)
-    sc = S["scale"] * Cf
-    amin, amax = cfg.constrains_area_minmax
-    area = (torch.clamp(amax - sc, min=0.0) + torch.clamp(sc - amin, min=0.0)).mean(1)
-    cx = (S["shift"][..., 0] + 1.0) * Cf / 2.0
-    cy = (S["shift"][..., 1] + 1.0) * Cf / 2.0
-    outl = (torch.clamp(-(cx - 0.5 * sc), min=0) + torch.clamp(-(cy - 0.5 * sc), min=0) +
-            torch.clamp(cx + 0.5 * sc - Cf, min=0) + torch.clamp(cy + 0.5 * sc - Cf, min=0)).sum(1)
-    size = torch.clamp((sc[:, :, None] - sc[:, None, :]).abs() - 3.0, min=0).sum((1, 2))
-    md = torch.maximum((cx[:, :, None] - cx[:, None, :]).abs(),
-                       (cy[:, :, None] - cy[:, None, :]).abs())
-    smean = (sc[:, :, None] + sc[:, None, :]) / 2.0
-    eye = torch.eye(Tx, dtype=dt)
-    over = (torch.clamp(smean - md, min=0) * (1.0 - eye)).sum((1, 2))
-    pr = (S["prn"].sum(1) + cfg.constrains_area_gamma * area + over * cfg.constrains_bbox_gamma +
-          outl * cfg.constrains_bbox_gamma + size * cfg.constrains_sharesize_gamma)
-    margin = torch.zeros((), dtype=dt)
-    elem = torch.zeros(B, dtype=dt)
-    if cfg.constrains_margin_gamma > 1e-8:
-        cons = list(cfg.constrains_num)
-        obj = torch.tensor([[1.0 if t < k else 0.0 for t in range(Tx)] for k in cons], dtype=dt)
-        mo = obj.mean(0)
-        if zsum_reduce is None:
-            pm = S["zprob"].mean(0)
-        else:  # global value, gradient through this shard's own terms only
-            zl = S["zprob"].sum(0)
-            zg = torch.as_tensor(zsum_reduce(zl.detach().clone()), dtype=dt)
-            pm = (zl + (zg - zl.detach())) / float(global_batch or B)
-        margin = (_sce(mo, _logit8(pm)) * cfg.constrains_margin_gamma).sum()
-        ce = _sce(obj[None], _logit8(S["zprob"])[:, None, :]).sum(2)
-        elem = ce.min(1).values * cfg.constrains_num_element_gamma
+    R = structural_terms(cfg, S["scale"], S["shift"], S["zprob"], S["prn"],
+                         zsum_reduce=zsum_reduce, global_batch=global_batch)
+    area, outl, size, over = R["area"], R["out"], R["size"], R["overlap"]
+    pr, margin, elem = R["pr"], R["margin"], R["element"]
     loss_b = elbo + pr + elem
     loss = loss_b.mean() * (B / float(global_batch or B)) + margin
     if canvas_cotangent is not None:

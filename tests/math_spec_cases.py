@@ -66,6 +66,13 @@ def oracle_math(fn: int, x: np.ndarray) -> np.ndarray:
     return y
 
 
+def logistic_noise(u: np.ndarray) -> np.ndarray:
+    """csrc/step_math.h logistic_noise restated: log(u + 1e-9) - log((1 - u) + 1e-9)."""
+    u = np.asarray(u, np.float32)
+    eps = np.float32(1e-9)
+    return oracle_math(LOG, u + eps) - oracle_math(LOG, (np.float32(1) - u) + eps)
+
+
 def same_bits(a: np.ndarray, b: np.ndarray) -> np.ndarray:
     """Element-wise: equal uint32 views, or both NaN."""
     a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)

@@ -23,6 +23,7 @@ from oracle import air_oracle as ao
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from math_spec_cases import EXP, LOG, NAMES, oracle_math, same_bits, spec_inputs  # noqa: E402
+from math_spec_cases import logistic_noise as _logistic_noise  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -67,11 +68,6 @@ def test_concrete_kl_device_equals_host():
     want = np.array([ao._load().oracle_concrete_kl(*(float(v) for v in row)) for row in grid], F)
     assert np.isfinite(want).all()
     _assert_same(_probe("concrete_kl", *cols), want, cols, "concrete_kl")
-
-
-def _logistic_noise(u):
-    eps = F(1e-9)
-    return oracle_math(LOG, u + eps) - oracle_math(LOG, (F(1) - u) + eps)
 
 
 def _lse0(a):
