@@ -718,6 +718,49 @@ int mog_asr_log_row(const float* arec, int NQ, const int* q, const float* vkl,
                     const float* element, const float* klsum, const float* margin,
                     const float* means, int T, int B, float* out, void* stream);
 
+/* ---- TensorBoard summaries on the device -------------------
+ * mog_summ_hist: TensorFlow's default histogram and the moments of every
+ * tensor of the flat fp32 buffer `buf` (`total` elements) in one call, over
+ * the optimizer's table (off / len [ntensors], block_tensor / block_start
+ * [nblocks], chunks of mog_optim_chunk_elems(); see mog_clip_adam).  Bucket
+ * limits: pos = 1e-12 * 1.1^k in double while < 1e20 (774 values), limits =
+ * [-DBL_MAX, -pos reversed, 0, pos, DBL_MAX] (1551); a value goes to the first
+ * limit greater than it.  thresholds [774]: the smallest fp32 above each pos
+ * (no pos is an fp32 value, so they classify exactly; compared, never
+ * recomputed).  sumsq == NULL: raw mode, every value as it is.  Otherwise
+ * applied mode: sumsq are the chunk sums mog_clip_adam left, each tensor's
+ * denom = fmaxf(norm, clip) is formed exactly as there and written to denom
+ * [ntensors], and every value is (g * clip) / denom without contraction (the
+ * bits Adam consumed); clip > 0.
+ * counts [ntensors][1551] uint32 and stats [ntensors][6] double = (min, max,
+ * num, sum, sum_squares, nonfinite) are fully written (no pre-zeroing); NaN
+ * and +-Inf are counted in nonfinite and nowhere else; min = DBL_MAX, max =
+ * -DBL_MAX where num == 0.  work: scratch of nblocks * 6 doubles.  Counts go
+ * through an LDS histogram and integer atomics, the moments through per-chunk
+ * partials added in chunk order: the same bits on every call.  Every table
+ * entry is clamped to the buffer. */
+int mog_summ_hist(const float* buf, long total, const long* off, const long* len,
+                  const int* block_tensor, const long* block_start, int nblocks, int ntensors,
+                  const float* thresholds, const float* sumsq, float clip, unsigned int* counts,
+                  double* stats, float* denom, double* work, void* stream);
+/* mog_summ_groups: the grouped sums of the reference's numeric summaries
+ * (air_model.py:216-264, 902-920) of one test chunk of B images.  target /
+ * steps [B] int32 (true and inferred object counts), bce / acc_b / loss_b [B],
+ * the records scale .. vkl [Tmax][B], live int32 [>= Tmax] (T_exec = the sum
+ * of live[0:Tmax], formed on the device).  acc [4 + 6 Tmax][max_digits + 2][2]
+ * double = (sum, count) per row and group (target == g for g <= max_digits,
+ * then all images), overwritten, or added to when accumulate != 0.  Rows: 0
+ * steps (as float), 1 bce, 2 acc_b, 3 loss_b, then 4 + q Tmax + i for step i
+ * of scale, zprob, zkl, skl, shkl, vkl (q = 0..5).  Masks: scale, skl, shkl,
+ * vkl steps > i; zkl steps > i - 1; the others none.  Entries of steps i >=
+ * T_exec count as 0.0 and are not read.  Sums run in double in an order fixed
+ * by B.  B >= 1, Tmax <= 8, max_digits <= 8. */
+int mog_summ_groups(const int* target, const int* steps, const float* bce, const float* acc_b,
+                    const float* loss_b, const float* scale, const float* zprob,
+                    const float* zkl, const float* skl, const float* shkl, const float* vkl,
+                    const int* live, int B, int Tmax, int max_digits, int accumulate, double* acc,
+                    void* stream);
+
 /* ---- measurement instrument (no reference counterpart) -------------------
  * dst[i] = src[i] for n4 float4s (16-byte aligned): the copy bandwidth the
  * bench quotes beside the HBM spec.  (The test-only instruments mog_spin and

@@ -1325,6 +1325,68 @@ void asr_log_row_(int64_t B, int64_t T, at::IntArrayRef slots, const Tensor& are
         o.name);
 }
 
+// TensorBoard summaries (mog_summ_hist / mog_summ_groups).
+// counts is an int32 tensor read as the kernel's uint32 (a count stays below
+// 2^31: a flat buffer of more elements is refused)
+void summ_hist_(const Tensor& buf, const Tensor& off, const Tensor& len,
+                const Tensor& block_tensor, const Tensor& block_start, int64_t nblocks,
+                int64_t ntensors, const Tensor& thresholds, const optional<Tensor>& sumsq,
+                double clip, Tensor counts, Tensor stats, const optional<Tensor>& denom,
+                Tensor work) {
+  Op o("summ_hist_");
+  const int64_t total = buf.numel();
+  TORCH_CHECK(nblocks >= 0 && ntensors >= 0 && nblocks <= INT32_MAX && ntensors <= INT32_MAX &&
+                  total <= INT32_MAX,
+              o.name, ": bad extents");
+  const bool applied = sumsq.has_value() && sumsq->defined();
+  TORCH_CHECK(!applied || (denom.has_value() && denom->defined() && clip > 0.0), o.name,
+              ": applied mode needs denom and clip > 0");
+  int* pc = o.i(counts, ntensors * 1551, "counts");
+  auto* pst = static_cast<double*>(o.need(stats, at::kDouble, ntensors * 6, "stats"));
+  float* pd = applied ? o.f(denom, ntensors, "denom") : nullptr;
+  auto* pw = static_cast<double*>(o.need(work, at::kDouble, nblocks * 6, "work"));
+  float* pb = o.f(buf, total, "buf");
+  auto* poff = static_cast<const long*>(o.need(off, at::kLong, ntensors, "off"));
+  auto* plen = static_cast<const long*>(o.need(len, at::kLong, ntensors, "len"));
+  const int* pbt = o.i(block_tensor, nblocks, "block_tensor");
+  auto* pbs = static_cast<const long*>(o.need(block_start, at::kLong, nblocks, "block_start"));
+  float* pt = o.f(thresholds, 774, "thresholds");
+  float* ps = applied ? o.f(sumsq, nblocks, "sumsq") : nullptr;
+  GUARD(o);
+  check(mog_summ_hist(pb, total, poff, plen, pbt, pbs, (int)nblocks, (int)ntensors, pt, ps,
+                      (float)clip, reinterpret_cast<unsigned int*>(pc), pst, pd, pw, o.stream()),
+        o.name);
+}
+
+void summ_groups_(const Tensor& target, const Tensor& steps, const Tensor& bce,
+                  const Tensor& acc_b, const Tensor& loss_b, const Tensor& scale,
+                  const Tensor& zprob, const Tensor& zkl, const Tensor& skl, const Tensor& shkl,
+                  const Tensor& vkl, const Tensor& live, int64_t B, int64_t Tmax,
+                  int64_t max_digits, bool accumulate, Tensor acc) {
+  Op o("summ_groups_");
+  TORCH_CHECK(B >= 1 && B <= INT32_MAX && Tmax >= 1 && Tmax <= 8 && max_digits >= 0 &&
+                  max_digits <= 8,
+              o.name, ": B >= 1, Tmax in 1..8, max_digits in 0..8");
+  auto* pa = static_cast<double*>(
+      o.need(acc, at::kDouble, (4 + 6 * Tmax) * (max_digits + 2) * 2, "acc"));
+  const int* ptg = o.i(target, B, "target");
+  const int* pst = o.i(steps, B, "steps");
+  float* pb = o.f(bce, B, "bce");
+  float* pab = o.f(acc_b, B, "acc_b");
+  float* pl = o.f(loss_b, B, "loss_b");
+  float* psc = o.f(scale, Tmax * B, "scale");
+  float* pzp = o.f(zprob, Tmax * B, "zprob");
+  float* pzk = o.f(zkl, Tmax * B, "zkl");
+  float* psk = o.f(skl, Tmax * B, "skl");
+  float* psh = o.f(shkl, Tmax * B, "shkl");
+  float* pvk = o.f(vkl, Tmax * B, "vkl");
+  const int* plv = o.i(live, Tmax, "live");
+  GUARD(o);
+  check(mog_summ_groups(ptg, pst, pb, pab, pl, psc, pzp, pzk, psk, psh, pvk, plv, (int)B,
+                        (int)Tmax, (int)max_digits, accumulate ? 1 : 0, pa, o.stream()),
+        o.name);
+}
+
 }  // namespace
 
 // split-K partials of the TN forms: reduce = 1 -> a transient [splitk][M][N]
@@ -1740,6 +1802,14 @@ TORCH_LIBRARY_FRAGMENT(mog_air, m) {
       "asr_log_row_(int B, int T, int[] slots, Tensor arec, Tensor vkl, Tensor zmask, "
       "Tensor live, Tensor bce, Tensor mse, Tensor area, Tensor outl, Tensor size, Tensor over, "
       "Tensor element, Tensor klsum, Tensor margin, Tensor means, Tensor(a!) out) -> ()");
+  m.def(
+      "summ_hist_(Tensor buf, Tensor off, Tensor len, Tensor block_tensor, Tensor block_start, "
+      "int nblocks, int ntensors, Tensor thresholds, Tensor? sumsq, float clip, "
+      "Tensor(a!) counts, Tensor(b!) stats, Tensor(c!)? denom, Tensor(d!) work) -> ()");
+  m.def(
+      "summ_groups_(Tensor target, Tensor steps, Tensor bce, Tensor acc_b, Tensor loss_b, "
+      "Tensor scale, Tensor zprob, Tensor zkl, Tensor skl, Tensor shkl, Tensor vkl, Tensor live, "
+      "int B, int Tmax, int max_digits, bool accumulate, Tensor(a!) acc) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(mog_air, CUDA, m) {
@@ -1805,4 +1875,6 @@ TORCH_LIBRARY_IMPL(mog_air, CUDA, m) {
   m.impl("asr_terms_backward_", &asr_terms_backward_);
   m.impl("asr_step_backward_", &asr_step_backward_);
   m.impl("asr_log_row_", &asr_log_row_);
+  m.impl("summ_hist_", &summ_hist_);
+  m.impl("summ_groups_", &summ_groups_);
 }

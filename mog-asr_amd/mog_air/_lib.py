@@ -101,6 +101,8 @@ _SIGS = {
     "mog_gather_rows": [P, P, P, I, I, I, P, P, P],
     "mog_synth_canvases": [P, P, I, P, I, I, ULL, ULL, I, P, P, P, P, P],
     "mog_asr_log_row": [P, I, P, P, P, P] + [P] * 10 + [I, I, P, P],
+    "mog_summ_hist": [P, L, P, P, P, P, I, I, P, P, F, P, P, P, P, P],
+    "mog_summ_groups": [P] * 12 + [I, I, I, I, P, P],
 }
 
 # entry points that do not return an int status

@@ -526,6 +526,125 @@ def gather_rows(src: torch.Tensor, idx, out: torch.Tensor, ksrc: Optional[torch.
     _ops.gather_rows_(src, ksrc, dev_idx, rows, width, B, out, kout)
 
 
+SUMM_NB, SUMM_NPOS, SUMM_NSTAT = 1551, 774, 6  # buckets, positive limits, stats columns
+SUMM_CAP = 8  # loop steps / object counts of the grouped-means kernel (= EVAL_CAP)
+
+
+def _same_device(ref: torch.Tensor, named) -> None:
+    for t, name in named:
+        if t.device != ref.device:
+            raise ValueError(f"{name} is on {t.device}, the op on {ref.device}")
+
+
+def summary_histograms(buf: torch.Tensor, t_off: torch.Tensor, t_len: torch.Tensor,
+                       t_bt: torch.Tensor, t_bs: torch.Tensor, n_blocks: int,
+                       thresholds: torch.Tensor, counts: torch.Tensor, stats: torch.Tensor,
+                       work: torch.Tensor, sumsq: Optional[torch.Tensor] = None,
+                       clip: Optional[float] = None,
+                       denom: Optional[torch.Tensor] = None) -> None:
+    """TensorFlow's default histogram and the moments of every variable of the
+    flat fp32 buffer ``buf`` over the optimizer's table (ParamStore.t_off,
+    t_len, t_bt, t_bs, n_blocks), in one call (mog_summ_hist): counts [V, 1551]
+    int32 and stats [V, 6] float64 = (min, max, num, sum, sum_squares,
+    nonfinite), both fully written.  ``thresholds`` [774] float32:
+    summaries.bucket_thresholds() on the device; ``work``: float64 scratch of
+    at least 6 * n_blocks.  Raw mode takes every value as it is.  Applied mode
+    (``sumsq``, ``clip`` and ``denom`` together): sumsq [n_blocks] are the
+    chunk sums the optimizer left, denom [V] float32 receives each tensor's
+    max(norm, clip), and every value is (g * clip) / denom, the bits Adam
+    consumed.  Everything is checked before the launch."""
+    _chk(buf, "buf")
+    _chk(counts, "counts", torch.int32)
+    _chk(stats, "stats", torch.float64)
+    _chk(work, "work", torch.float64)
+    _chk(thresholds, "thresholds")
+    _chk(t_off, "t_off", torch.int64)
+    _chk(t_len, "t_len", torch.int64)
+    _chk(t_bt, "t_bt", torch.int32)
+    _chk(t_bs, "t_bs", torch.int64)
+    if buf.dim() != 1:
+        raise ValueError(f"buf must be a flat buffer, got {tuple(buf.shape)}")
+    if t_off.dim() != 1 or t_off.shape != t_len.shape:
+        raise ValueError("t_off and t_len must be [V] alike")
+    V, n_blocks = t_off.shape[0], int(n_blocks)
+    if n_blocks < 0 or tuple(t_bt.shape) != (n_blocks,) or tuple(t_bs.shape) != (n_blocks,):
+        raise ValueError(f"t_bt and t_bs must be [{n_blocks}] (n_blocks), got "
+                         f"{tuple(t_bt.shape)} and {tuple(t_bs.shape)}")
+    if tuple(counts.shape) != (V, SUMM_NB) or tuple(stats.shape) != (V, SUMM_NSTAT):
+        raise ValueError(f"counts must be [{V}, {SUMM_NB}] and stats [{V}, {SUMM_NSTAT}], got "
+                         f"{tuple(counts.shape)} and {tuple(stats.shape)}")
+    if tuple(thresholds.shape) != (SUMM_NPOS,):
+        raise ValueError(f"thresholds must be [{SUMM_NPOS}], got {tuple(thresholds.shape)}")
+    if work.numel() < 6 * n_blocks:
+        raise ValueError(f"work holds {work.numel()} values, the call needs {6 * n_blocks}")
+    named = [(t_off, "t_off"), (t_len, "t_len"), (t_bt, "t_bt"), (t_bs, "t_bs"),
+             (thresholds, "thresholds"), (counts, "counts"), (stats, "stats"), (work, "work")]
+    applied = sumsq is not None or clip is not None or denom is not None
+    if applied:
+        if sumsq is None or clip is None or denom is None:
+            raise ValueError("applied mode takes sumsq, clip and denom together")
+        _chk(sumsq, "sumsq")
+        _chk(denom, "denom")
+        if tuple(sumsq.shape) != (n_blocks,):
+            raise ValueError(f"sumsq must be [{n_blocks}] (the table's n_blocks), got "
+                             f"{tuple(sumsq.shape)}")
+        if tuple(denom.shape) != (V,):
+            raise ValueError(f"denom must be [{V}], got {tuple(denom.shape)}")
+        if not float(clip) > 0.0:
+            raise ValueError(f"clip must be positive, got {clip}")
+        named += [(sumsq, "sumsq"), (denom, "denom")]
+    _same_device(buf, named)
+    _ops.summ_hist_(buf, t_off, t_len, t_bt, t_bs, n_blocks, V, thresholds, sumsq,
+                    float(clip) if applied else 0.0, counts, stats, denom, work)
+
+
+def summary_groups(target: torch.Tensor, steps: torch.Tensor, bce: torch.Tensor,
+                   acc_b: torch.Tensor, loss_b: torch.Tensor, scale: torch.Tensor,
+                   zprob: torch.Tensor, zkl: torch.Tensor, skl: torch.Tensor, shkl: torch.Tensor,
+                   vkl: torch.Tensor, live: torch.Tensor, max_digits: int, acc: torch.Tensor,
+                   accumulate: bool = False) -> None:
+    """The grouped sums of the numeric summaries of one test chunk
+    (mog_summ_groups): target / steps [B] int32, bce / acc_b / loss_b [B], the
+    six records [Tmax, B], live int32 [Tmax] or [Tmax + 1] -> acc [4 + 6 Tmax,
+    max_digits + 2, 2] float64 = (sum, count) per row and group (the object
+    counts 0..max_digits, then all images), overwritten or, with
+    ``accumulate``, added to.  Record rows at or beyond the executed steps (the
+    sum of live[:Tmax], formed on the device) count as 0.0 and are not read.
+    B >= 1, Tmax, max_digits <= 8."""
+    _chk(acc, "acc", torch.float64)
+    _chk(target, "target", torch.int32)
+    _chk(steps, "steps", torch.int32)
+    _chk(live, "live", torch.int32)
+    if target.dim() != 1 or target.shape[0] < 1:
+        raise ValueError(f"target must be [B >= 1], got {tuple(target.shape)}")
+    B = target.shape[0]
+    if scale.dim() != 2 or scale.shape[1] != B:
+        raise ValueError(f"scale must be [Tmax, {B}], got {tuple(scale.shape)}")
+    Tmax, max_digits = scale.shape[0], int(max_digits)
+    if not 1 <= Tmax <= SUMM_CAP or not 0 <= max_digits <= SUMM_CAP:
+        raise ValueError(f"{Tmax} loop steps, {max_digits} objects: the kernel holds 1..{SUMM_CAP} "
+                         f"steps and 0..{SUMM_CAP} objects")
+    named = [(target, "target"), (steps, "steps"), (live, "live")]
+    for t, name, shape in ((steps, "steps", (B,)), (bce, "bce", (B,)), (acc_b, "acc_b", (B,)),
+                           (loss_b, "loss_b", (B,)), (scale, "scale", (Tmax, B)),
+                           (zprob, "zprob", (Tmax, B)), (zkl, "zkl", (Tmax, B)),
+                           (skl, "skl", (Tmax, B)), (shkl, "shkl", (Tmax, B)),
+                           (vkl, "vkl", (Tmax, B))):
+        if name != "steps":
+            _chk(t, name)
+            named.append((t, name))
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {list(shape)}, got {tuple(t.shape)}")
+    if live.dim() != 1 or live.shape[0] not in (Tmax, Tmax + 1):
+        raise ValueError(f"live must be [{Tmax}] or [{Tmax + 1}], got {tuple(live.shape)}")
+    rows = 4 + 6 * Tmax
+    if tuple(acc.shape) != (rows, max_digits + 2, 2):
+        raise ValueError(f"acc must be [{rows}, {max_digits + 2}, 2], got {tuple(acc.shape)}")
+    _same_device(acc, named)
+    _ops.summ_groups_(target, steps, bce, acc_b, loss_b, scale, zprob, zkl, skl, shkl, vkl, live,
+                      B, Tmax, max_digits, bool(accumulate), acc)
+
+
 SYNTH_SIDE, SYNTH_GMAX, SYNTH_MAX_INDEX = 32, 8, 2 ** 52
 
 

@@ -12,8 +12,10 @@ which the entry points pass by name.
 Image grids (training_air_original.py:368-411, :445-490): every
 IMAGE_SAVE_ITERATION iterations and at the end, the test model's
 reconstruction / misclassified / generation grids are written as PNG files
-under summary/ (``mog_air.visualize``).  TensorBoard event files are out of
-scope.
+under summary/ (``mog_air.visualize``).  With --summaries 1 the reference's
+TensorBoard summaries (training_air_original.py:223-301) are computed on the
+device and written as an event file beside them (``mog_air.summaries``,
+DESIGN.md §4.19).
 
 Checkpoints: ``Saver`` writes the variables (models/air-model-<step>.npz),
 ``StateSaver`` the full train state beside them (models/air-state-<step>.npz,
@@ -51,7 +53,7 @@ def add_common_args(parser, reader_threads: int):
     reference): --iterations, --precision, --test-batch, --synth-per-count,
     --write-synthetic, --device, --resident, --save-every, --restore,
     --restore-mode, --eval-only, --batch-size, --stream, --stream-seed,
-    --graph."""
+    --graph, --summaries, --summary-cadence."""
     parser.add_argument("-r", "--results-folder", default="Not Valid")
     parser.add_argument("-k", "-key", "--key", default="")
     parser.add_argument("-gpu", "--gpu", default="-1")
@@ -98,6 +100,13 @@ def add_common_args(parser, reader_threads: int):
                         help="1: every iteration is the captured train step "
                              "(train_step_graphed) and its log row stays on the device until a "
                              "log line or a state save needs it (LogRing); one device only")
+    parser.add_argument("--summaries", type=int, choices=[0, 1], default=0,
+                        help="1: the reference's TensorBoard summaries, computed on the device, "
+                             "as an event file under summary/ (summaries.Summaries); one "
+                             "device only")
+    parser.add_argument("--summary-cadence", default="50,250,500,100", metavar="NUM,VAR,IMG,GRAD",
+                        help="iterations between two numeric / variable / image / gradient "
+                             "summaries (training_air_original.py:33-36)")
 
 
 def select_gpu(gpu: str) -> None:
@@ -235,6 +244,19 @@ def check_graph_args(args, ctx: Dist, annealed=()) -> None:
         raise ValueError("--graph 1: annealed %s would be frozen at capture" % frozen)
 
 
+def check_summary_args(args, ctx: Dist) -> None:
+    """--summaries 1: refused before anything is written with a malformed
+    --summary-cadence or more than one rank (the fetches read one device's
+    train state)."""
+    if not getattr(args, "summaries", 0):
+        return
+    from .summaries import parse_cadence
+    parse_cadence(getattr(args, "summary_cadence", "50,250,500,100"))
+    if ctx.world > 1:
+        raise ValueError("--summaries 1 reads the single-device train state, but this run has "
+                         "%d ranks" % ctx.world)
+
+
 def results_folder(args, entry: str, name: str, main: bool = True) -> str:
     """training_air_original.py:93-115: default name, -k suffix, -o overwrite
     or the next free _N suffix; creates models/, summary/, source/ (rank 0
@@ -344,6 +366,7 @@ def setup_run(args, entry: str, annealed=()):
     check_feed_args(args, train_file, test_file)
     ctx = distributed_setup(args)  # one process per GPU under torch.distributed.run
     check_graph_args(args, ctx, annealed=annealed)
+    check_summary_args(args, ctx)
     folder = results_folder(args, entry, name, main=ctx.main)
     log = build_logger(folder, args, main=ctx.main)
     if ctx.main:
@@ -609,6 +632,7 @@ class AirStyle:
     step's [loss, accuracy, mse] is a row of LoopState.rows; the best results
     follow the periodic tests only, and the final test is tagged 'final'."""
     grids_per_count = True  # generation grids for every object count of -dn
+    full_summaries = True   # --summaries 1: numeric and image summaries too
 
     def step_row(self, model, fetched):
         return list(fetched[:3])
@@ -617,12 +641,14 @@ class AirStyle:
         st.rows.extend(rows)
 
     def log_line(self, st, model, mean):
-        """(train loss, log line) of the rows since the last log line (the
-        last LOG_EACH_ITERATION), which are dropped."""
+        """(train loss, log line, the line's (name, mean) pairs) of the rows
+        since the last log line (the last LOG_EACH_ITERATION), which are
+        dropped."""
         l0, l1, l2 = mean(np.mean(st.rows, axis=0))
         st.rows = []
         return l0, ("iteration {}\ttrain loss {:.3f}\ttrain accuracy {:.2f}, "
-                    "train mse {:.3f}".format(st.step, l0, l1, l2))
+                    "train mse {:.3f}".format(st.step, l0, l1, l2)), \
+            list(zip(model.log_names, (l0, l1, l2)))
 
     def report(self, log, st, final, sums, detections, test_model):
         log.info("iteration {}\ttest loss {:.3f}\ttest accuracy {:.2f}, test mse {:.3f}".format(
@@ -641,6 +667,7 @@ class AsrStyle:
     one included, is tagged with the step (train_air_pr.py:426-430), logs the
     test model's log variables and is followed by the best results."""
     grids_per_count = False  # train_air_pr.py:362-398: the model's loop draws the counts
+    full_summaries = False   # train_air_pr.py has the numeric / image summaries commented out
 
     def step_row(self, model, fetched):
         return list(model.log_variables.values())
@@ -651,14 +678,14 @@ class AsrStyle:
                 st.logged.setdefault(n, []).append(v)
 
     def log_line(self, st, model, mean):
-        """(TotLoss, log line) of the variables since the last log line, which
-        are dropped: the means in the model's order (a restored ``logged`` may
-        list them in another)."""
+        """(TotLoss, log line, the line's (name, mean) pairs) of the variables
+        since the last log line, which are dropped: the means in the model's
+        order (a restored ``logged`` may list them in another)."""
         names = model.log_names
         means = mean([np.mean(st.logged[n]) for n in names])
         st.logged = {}
         return float(means[names.index("TotLoss")]), "step:{:6d}\t".format(st.step) + "".join(
-            "{}:{:.4f}\t".format(n, v) for n, v in zip(names, means))
+            "{}:{:.4f}\t".format(n, v) for n, v in zip(names, means)), list(zip(names, means))
 
     def report(self, log, st, final, sums, detections, test_model):
         d = detections()
@@ -728,8 +755,22 @@ def train_loop(args, train_model, test_model, tr_x, tr_k, test, canvas, log, mod
         save_visualizations(test_model, test[0][:vis_n], test[1][:vis_n], summary_folder, tag,
                             digits=digits, num=NUM_IMAGES_TO_SAVE, gen_tag=gen_tag)
 
+    # --summaries 1: the reference's TensorBoard summaries into a new event
+    # file (also after --restore: nothing of the writer is restored)
+    summ = None
+    if getattr(args, "summaries", 0) and ctx.main and not args.eval_only:
+        from .summaries import Summaries, parse_cadence
+        summ = Summaries(summary_folder, train_model.params, parse_cadence(args.summary_cadence),
+                         full=style.full_summaries, log=log)
+    summ_test = test_dev if test_dev is not None else test
+
     log.info("Training...\n")
     while not args.eval_only:
+        pre_step = st.step
+        if summ is not None:
+            # training_air_original.py:252-283: before the save and the step
+            summ.before_step(pre_step, test_model, summ_test[0], summ_test[1], args.test_batch,
+                             vis_n=vis_n)
         if args.save_every > 0 and st.step % args.save_every == 0:
             if ctx.main:
                 saver.save(train_model.params, st.step)
@@ -746,12 +787,17 @@ def train_loop(args, train_model, test_model, tr_x, tr_k, test, canvas, log, mod
             fetched = train_model.step(x, k, global_batch=nglobal)
             st.step = fetched[3]
             style.keep(st, train_model, [style.step_row(train_model, fetched)])
+        if summ is not None and summ.wants_gradients(pre_step):
+            # :290-301: the gradients this step applied, under the post-step number
+            summ.gradients(train_model.params, train_model.gradient_clipping_norm, st.step)
         if st.step % LOG_EACH_ITERATION == 0:
             drain()
             # the global batch's means (shard-size weighted over ranks)
-            loss, line = style.log_line(
+            loss, line, pairs = style.log_line(
                 st, train_model, lambda v: ctx.mean(v, args.device, weight=len(k)))
             log.info(line)
+            if summ is not None:
+                summ.scalars([("train/" + n, v) for n, v in pairs], st.step)
             if loss < st.min_loss:
                 st.update_flag, st.min_loss = True, loss
         # (train_air_pr.py:31 spells its constant TESET_EACH_ITERATION; both are 200)
@@ -771,6 +817,8 @@ def train_loop(args, train_model, test_model, tr_x, tr_k, test, canvas, log, mod
     # final generation grids with the step (training_air_original.py:478-483,
     # train_air_pr.py:462-469)
     save_images("final", gen_tag=st.step)
+    if summ is not None:
+        summ.close()
     log.info(BEST.format("Final", *st.best))
     log.info("\ntraining has ended\n")
     return st.step

@@ -29,8 +29,8 @@ COLORS = np.array([[1., 0., 0.], [0., 1., 0.], [0., 0., 1.], [1., 1., 0.], [1., 
                    [0., 1., 1.]], np.float32)
 
 
-def write_png(path: str, rgb: np.ndarray) -> None:
-    """8-bit RGB PNG (filter 0 per scanline)."""
+def png_bytes(rgb: np.ndarray) -> bytes:
+    """8-bit RGB PNG (filter 0 per scanline) of [H, W, 3]."""
     rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
     h, w, c = rgb.shape
     assert c == 3
@@ -41,9 +41,12 @@ def write_png(path: str, rgb: np.ndarray) -> None:
         return struct.pack(">I", len(data)) + body + struct.pack(">I", zlib.crc32(body) & 0xFFFFFFFF)
 
     png = b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
-    png += chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b"")
+    return png + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b"")
+
+
+def write_png(path: str, rgb: np.ndarray) -> None:
     with open(path, "wb") as f:
-        f.write(png)
+        f.write(png_bytes(rgb))
 
 
 def pile_image(images: np.ndarray, path: str, shape=None) -> None:
